@@ -23,9 +23,16 @@ the device by the counter-based generator of spatialflink_amd.synth; Gaussian wi
 host by synth.gaussian_clusters then copied).  A ring of distinct windows (> 256 MiB in total)
 is cycled so no step reads a window the Infinity Cache still holds.
 
-Prints ONE JSON line (rank 0) with roofline and cpu_baseline objects.
+A plain run sets up, warms up, times the steps and prints ONE JSON line (rank 0): the headline
+rate, ms_per_step and the roofline object read from the timed steps' own dispatch stamps.
+``--full`` adds what takes runs of its own after the timed region: the check of the timed steps'
+results against the synchronous calls (counts_verified), the cpu_baseline object, the key-band
+layout side line, the host-resident end-to-end and pipelined lines (knn) and the fp64 object
+(point-polygon workloads).  ``--dump-outputs DIR`` writes what the last timed step handed its
+caller as DIR/<name>.npy (float64; sets and pair lists sorted, a fixed seeded sample of an output
+over 64 MB), so two builds can be compared output for output: the inputs are seeded.
 
-    python bench.py --gpus 1 --steps 50 --warmup 5 [--workload knn|range|join|ppoly|c5|ingest|ppjoin|ppknn|knn_incr|ppoly_incr]
+    python bench.py --gpus 1 --steps 50 --warmup 5 [--full] [--dump-outputs DIR] [--workload knn|range|join|ppoly|c5|ingest|ppjoin|ppknn|knn_incr|ppoly_incr]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -58,6 +65,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--workload", choices=("knn", "range", "join", "ppoly", "c5", "ingest", "ppjoin", "ppknn", "knn_incr", "ppoly_incr"), default="knn")
     p.add_argument("--points", type=int, default=None, help="points per window per GPU (default: the config's)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline figure does not need: the check of the "
+                        "timed results against the synchronous calls, the CPU baseline, the key-band side line, the "
+                        "end-to-end and pipelined lines (knn) and the fp64 object (point-polygon workloads); the "
+                        "--no-* options below trim that set")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step handed its caller as DIR/<name>.npy (float64; at most 64 MB "
+                        "in all, a fixed seeded sample of a larger output)")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--range-ascending", action="store_true",
@@ -76,7 +91,10 @@ def parse():
                         "steps): a stamped dispatch costs the step ~4 us of launch (C2: 44.4 us per step with "
                         "every step stamped, 40.4 with every 5th, 40.1 with one), so stamping them all would "
                         "lower the measured rate")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _oracle():
@@ -104,6 +122,43 @@ def pmc_traffic(kernel_tag: str, key: str = "hbm_bytes_per_launch"):
         except Exception:
             return None
     return None
+
+
+DUMP_CAP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all arrays together, as float64
+
+
+def _host(t, count=None):
+    """Device tensor (its first `count` rows) -> numpy."""
+    if count is not None:
+        t = t[:int(count)]
+    return t.detach().cpu().numpy()
+
+
+def _sorted_set(a):
+    """An unordered hit set as the ascending array (the order of a set is not part of the result)."""
+    return np.sort(np.asarray(a).astype(np.int64))
+
+
+def _sorted_pairs(a):
+    """A pair list [m, 2] in lexicographic row order (a join's pair order is not part of the result)."""
+    a = np.asarray(a).reshape(-1, 2).astype(np.int64)
+    return a[np.lexsort((a[:, 1], a[:, 0]))]
+
+
+def dump_outputs(directory, arrays):
+    """Write {name: array} as directory/<name>.npy in float64.  Over DUMP_CAP_BYTES in all, each
+    array keeps the same fraction of its rows: a fixed seeded sample, rows in their own order."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    total = sum(8 * a.size for a in arrays.values())
+    frac = min(1.0, DUMP_CAP_BYTES / total) if total else 1.0
+    for i, (name, a) in enumerate(sorted(arrays.items())):
+        if frac < 1.0 and a.ndim >= 1 and len(a) > 1:
+            keep = max(1, int(len(a) * frac))
+            rows = np.sort(np.random.default_rng(1234 + i).choice(len(a), keep, replace=False))
+            a = a[rows]
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -142,6 +197,9 @@ class Workload:
 
     def verify(self) -> bool | None:  # after the timed region: the async steps' device counts
         return None
+
+    def outputs(self) -> dict:  # --dump-outputs: what the last step handed its caller, {name: host array}
+        raise NotImplementedError
 
     def _timed_side(self, fn, steps):
         """Max-over-ranks wall time of `steps` calls of fn(s) (barrier + synchronize around)."""
@@ -342,6 +400,28 @@ class KnnWorkload(Workload):
             ok = int(self.out_rc[j].item()) == len(want)
         return ok
 
+    def outputs(self):
+        """The last step's top-k (N > 1: the merged one) and, for C5, its range hit set."""
+        import torch
+        torch.cuda.synchronize(self.dev)
+        if self.args.partition == "cells":
+            res, (hits, _, total), _ = self.cells_last.result()
+            o = {"knn_idx": _host(res.idx), "knn_dist": _host(res.dist)}
+            if self.has_range:
+                o["range_hits"] = _sorted_set(_host(hits))  # this rank's band
+                o["range_total"] = np.array([int(total)])
+            return o
+        j = self.last_s & 1
+        if self.world > 1:
+            m = int(self.mcnt.item())
+            o = {"knn_idx": _host(self.m_i, m), "knn_dist": _host(self.m_d, m)}
+        else:
+            m = int(self.cnt[0].item())
+            o = {"knn_idx": _host(self.out_i[j], m), "knn_dist": _host(self.out_d[j], m)}
+        if self.has_range:
+            o["range_hits"] = _sorted_set(_host(self.rout, self.out_rc[j].item()))  # this rank's shard
+        return o
+
     def step(self, s):
         import torch
         if self.args.partition == "cells":
@@ -539,6 +619,10 @@ class RangeWorkload(Workload):
         return torch.equal(torch.sort(self.out[:m].to(torch.int64)).values.cpu(),
                            torch.sort(want[w].to(torch.int64)).values.cpu())
 
+    def outputs(self):  # the last step's hits (this rank's shard), ascending
+        self.ctx.sync()
+        return {"range_hits": _sorted_set(_host(self.out, self.cnt[self.last_w].item()))}
+
     def algorithmic_bytes(self):
         if self.hits is None:
             self.hits = float(self.cnt.double().mean().item())
@@ -639,7 +723,7 @@ class JoinWorkload(Workload):
 
     def step(self, s):
         import torch
-        w = s % self.windows
+        w = self.last_w = s % self.windows
         if self.args.partition == "cells":
             self.cells_last = self.cells_window(w)  # (this rank's pairs, offset, window total)
             return
@@ -654,6 +738,12 @@ class JoinWorkload(Workload):
             return None
         self.ctx.sync()  # faults of the async steps (query keys) raise here
         return self.cnt.cpu().tolist() == self.pairs
+
+    def outputs(self):  # the last step's (data, query) pairs of this rank, in row order
+        self.ctx.sync()
+        if self.args.partition == "cells":
+            return {"join_pairs": _sorted_pairs(_host(self.cells_last.result()[0]))}
+        return {"join_pairs": _sorted_pairs(_host(self.out, self.cnt[self.last_w].item()))}
 
     def check_merged(self, last_step):
         """N > 1, key-band step (--check): the window's pair total over the band owners against the
@@ -730,7 +820,7 @@ class PpolyWorkload(Workload):
         return self.n
 
     def step(self, s):
-        w = s % self.windows
+        w = self.last_w = s % self.windows
         # enqueue-only (geohip_range_ppoly_async): no end-of-step count readback
         self.ctx.range_ppoly_async(self.grid, self.xs[w], self.ys[w], self.off, self.vx, self.vy, self.radius, False,
                                    self.out, self.cnt[w:w + 1])
@@ -738,6 +828,10 @@ class PpolyWorkload(Workload):
     def verify(self):
         self.ctx.sync()  # a candidate-buffer overflow of an async step raises here
         return self.cnt.cpu().tolist() == self.hits
+
+    def outputs(self):  # the last step's (polygon, point) pairs, in row order
+        self.ctx.sync()
+        return {"ppoly_pairs": _sorted_pairs(_host(self.out, self.cnt[self.last_w].item()))}
 
     def algorithmic_bytes(self):
         return BYTES_PER_POINT * self.n + 16 * len(self.vx) + 8 * float(np.mean(self.hits))
@@ -825,7 +919,7 @@ class PpJoinWorkload(PpolyWorkload):
         self.cnt = torch.zeros(self.windows, dtype=torch.int64, device=self.dev)
 
     def step(self, s):
-        w = s % self.windows
+        w = self.last_w = s % self.windows
         self.ctx.join_ppoly_async(self.grid, self.grid, self.xs[w], self.ys[w], self.off, self.vx, self.vy,
                                   self.radius, False, self.out, self.cnt[w:w + 1])
 
@@ -885,6 +979,11 @@ class PpKnnWorkload(Workload):
         self.ctx.knn_ppoly_async(self.grid, self.xs[w], self.ys[w], self.vx, self.vy, self.radius, self.k, False,
                                  self.oi, self.od, self.oc)
 
+    def outputs(self):
+        self.ctx.sync()
+        m = int(self.oc.item())
+        return {"knn_idx": _host(self.oi, m), "knn_dist": _host(self.od, m)}
+
     def algorithmic_bytes(self):
         return BYTES_PER_POINT * self.n
 
@@ -940,6 +1039,11 @@ class PpolyIncrWorkload(PpolyWorkload):
         # enqueue-only pane (geohip_range_ppoly_pane_async): no end-of-step count readback
         self.inc.push(self.xs[w], self.ys[w], out=self.outs[s % 2], count=self.pcnt[w])
 
+    def outputs(self):  # the last window's (polygon, stream position) pairs: its two panes', in row order
+        self.ctx.sync()
+        panes = [_host(out, count.item()).reshape(-1, 2) for out, count in self.inc.window()]
+        return {"ppoly_pairs": _sorted_pairs(np.concatenate(panes))}
+
     def config(self):
         c = super().config()
         c["workload"] = (f"C4 over 10s/5s sliding windows with pane reuse: {self.npoly} polygons x 50 vertices, "
@@ -974,6 +1078,12 @@ class KnnIncrWorkload(KnnWorkload):
 
     def verify(self):  # the pane merges are checked by tests/test_gpu_incremental.py
         return None
+
+    def outputs(self):  # the last window's top-k, merged from its two panes
+        import torch
+        torch.cuda.synchronize(self.dev)
+        m = int(self.inc.cnt[1].item())
+        return {"knn_idx": _host(self.inc.mi, m), "knn_dist": _host(self.inc.md, m)}
 
     def config(self):
         c = super().config()
@@ -1080,7 +1190,12 @@ class IngestWorkload(Workload):
         return self.n
 
     def step(self, s):
-        self.ctx.ingest_points(self.spec, self.text, self.grid, with_ts=True, with_cell=True, cap=self.n, out=self.out)
+        self.got = self.ctx.ingest_points(self.spec, self.text, self.grid, with_ts=True, with_cell=True, cap=self.n,
+                                          out=self.out)
+
+    def outputs(self):  # the last batch's parsed columns
+        self.ctx.sync()
+        return {name: _host(col) for name, col in self.got.items() if name in ("x", "y", "ts", "cell")}
 
     def algorithmic_bytes(self):  # text read once + x, y, ts, cell written
         return self.nbytes + (8 + 8 + 8 + 4) * self.n
@@ -1168,7 +1283,10 @@ def main():
     elapsed = time.perf_counter() - t0
     ctx.set_timing(False)
     step_ms, launches, kern_ms, kernels = ctx.timing_kernels(reset=True)
-    verified = wl.verify()  # the enqueue-only steps' device counts against the counts of __init__
+    if args.dump_outputs:  # before anything else runs: the last timed step's own results
+        dump_outputs(Path(args.dump_outputs) if world == 1 else Path(args.dump_outputs) / f"rank{rank}", wl.outputs())
+    # --full: the enqueue-only steps' device counts against the counts of __init__
+    verified = wl.verify() if args.full else None
     if verified is False:
         raise SystemExit(f"bench: {args.workload} steps returned counts that differ from the synchronous calls'")
     if dist:
@@ -1212,7 +1330,7 @@ def main():
         "roofline": roofline,
         "cpu_baseline": None,
     }
-    alg_flops = wl.algorithmic_flops() if hasattr(wl, "algorithmic_flops") else None
+    alg_flops = wl.algorithmic_flops() if args.full and hasattr(wl, "algorithmic_flops") else None
     if alg_flops and avg_s > 0:  # the point-polygon steps: FP64 is not their bound
         pmc_flops = pmc_traffic(wl.tag, "fp64_flops_per_launch")
         result["fp64"] = {
@@ -1231,19 +1349,19 @@ def main():
         ok = wl.check_merged(args.warmup + args.steps - 1)
         if rank == 0 and ok is not None:
             result["merged_matches_full_window"] = ok
-    if not args.no_cells_line and args.partition == "arrival":
+    if args.full and not args.no_cells_line and args.partition == "arrival":
         cells = wl.cells_partition(args.cells_steps)
         if cells is not None and rank == 0:
             result["partition_cells"] = cells
     if args.partition == "cells":
         result["config"]["parallelism"] = f"key-band{world} (north-star layout)"
-    if rank == 0 and world == 1 and not args.no_e2e and args.workload == "knn":  # the C2 host path
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and args.workload == "knn":  # the C2 host path
         e2e = wl.e2e()
         if e2e is not None:
             result["e2e"] = e2e
-    if rank == 0 and world == 1 and args.workload == "knn" and not args.no_pipelined:
+    if args.full and rank == 0 and world == 1 and args.workload == "knn" and not args.no_pipelined:
         result["pipelined"] = wl.pipelined(nstreams=args.pipeline_streams)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = wl.cpu_baseline(args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -10,12 +10,12 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for w in ${WORKLOADS:-knn range c5 join ppoly ingest ppjoin ppknn knn_incr ppoly_incr}; do
   steps=50; [ "$w" = "join" ] || [ "$w" = "ppoly" ] || [ "$w" = "ppjoin" ] && steps=20
-  timeout -k 10 300 python -u bench.py --workload "$w" --steps $steps --warmup 3 > $OUT/bench_$w.log 2>&1 \
+  timeout -k 10 300 python -u bench.py --full --workload "$w" --steps $steps --warmup 3 > $OUT/bench_$w.log 2>&1 \
       || { echo "bench $w failed"; tail -20 $OUT/bench_$w.log; exit 2; }
   grep '^{' $OUT/bench_$w.log | cut -c1-120
 done
 if [ "${DEFAULT:-1}" = "1" ]; then
-  timeout -k 10 300 python -u bench.py > $OUT/bench_default.log 2>&1 || { echo "bench default failed"; exit 3; }
+  timeout -k 10 300 python -u bench.py --full > $OUT/bench_default.log 2>&1 || { echo "bench default failed"; exit 3; }
   grep '^{' $OUT/bench_default.log | cut -c1-120
 fi
 if [ "${EXTRA:-1}" = "1" ]; then

@@ -12,7 +12,7 @@ if [ "${TESTS:-1}" = "1" ]; then
 fi
 for w in ${WORKLOADS:-knn range c5 join ppoly ingest ppjoin ppknn knn_incr ppoly_incr}; do
   steps=50; [ "$w" = "join" ] || [ "$w" = "ppoly" ] || [ "$w" = "ppjoin" ] && steps=20
-  timeout -k 10 300 python -u bench.py --workload "$w" --steps $steps --warmup 3 \
+  timeout -k 10 300 python -u bench.py --full --workload "$w" --steps $steps --warmup 3 \
       > gpurun_out/final/bench_$w.log 2>&1 || { echo "bench $w failed"; tail -20 gpurun_out/final/bench_$w.log; exit 2; }
   grep '^{' gpurun_out/final/bench_$w.log | cut -c1-160
   [ "${PROF:-1}" = "1" ] || continue

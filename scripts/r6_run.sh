@@ -8,6 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=${OUT:-gpurun_out/r6}
 mkdir -p "$OUT/prof"
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole record: result check, CPU baseline, side lines
 if [ "${TESTS:-1}" = "1" ]; then
   KA=(); [ -n "${K:-}" ] && KA=(-k "$K")
   # test failures (exit 1) are reported and the run goes on; anything else (a timeout, a crash,

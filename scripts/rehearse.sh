@@ -13,7 +13,7 @@ for wl in ${WORKLOADS:-knn c5 join}; do
       log=gpurun_out/rehearse/w${w}_${wl}_${part}.log
       GEOHIP_BENCH_ONE_DEVICE=1 GEOHIP_BENCH_BACKEND=gloo timeout -k 10 ${TMO:-420} \
         python -m torch.distributed.run --nnodes=1 --nproc-per-node $w --master-addr 127.0.0.1 --master-port $port \
-        bench.py --gpus $w --workload $wl --steps ${STEPS:-4} --warmup 1 --no-cpu-baseline --check \
+        bench.py --gpus $w --workload $wl --steps ${STEPS:-4} --warmup 1 --full --no-cpu-baseline --check \
         --partition $part --cells-steps 3 > $log 2>&1 || { echo "FAILED $log"; tail -30 $log; exit 1; }
       grep '^{' $log > gpurun_out/rehearse/w${w}_${wl}_${part}.json
       echo "ok $log"
