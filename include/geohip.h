@@ -20,7 +20,11 @@
  *                         (one independent query per polygon)
  *   geohip_ingest_points <- Deserialization.PointStream / TrajectoryStream map functions
  *                         spatialStreams/Deserialization.java:47-80, 132-146, 223-228, 248-254, 306-321
- *   geohip_grid        <- UniformGrid getters                         spatialIndices/UniformGrid.java:136-146
+ *   geohip_traj_group  <- keyBy(objID) + trajIDSet filter of the trajectory operators
+ *                         spatialOperators/tStats/PointTStatsQuery.java:76-92, tFilter/PointTFilterQuery.java:89-107
+ *   geohip_tstats      <- TStatsQueryWFunction.apply                  spatialOperators/tStats/TStatsQuery.java:148-189
+ *   geohip_traj_gather <- PointTFilterQuery's window function         spatialOperators/tFilter/PointTFilterQuery.java:100-118
+ *   geohip_grid        <- UniformGrid getters                        spatialIndices/UniformGrid.java:136-146
  *                         (values copied from the Java object, so both constructors :47-85 are covered)
  *
  * Semantics (bit-exact contract, DESIGN.md "Parity"):
@@ -460,6 +464,55 @@ int geohip_ingest_trajectory(geohip_ctx* ctx, const geohip_grid* grid, const geo
    untouched). */
 int geohip_ingest_oid_compact(geohip_ctx* ctx, const char* text, uint64_t nbytes, const uint64_t* oid_spans,
                               uint64_t m, uint8_t* out_text, uint64_t cap, uint64_t* out_off, uint64_t* out_len);
+
+/* ---- trajectory queries keyed by objID ------------------------------------------------ */
+/* The trajectory operators' keyBy(p -> p.objID) over one window, with their trajIDSet filter
+   (spatialOperators/tStats/PointTStatsQuery.java:76-92, tFilter/PointTFilterQuery.java:89-107).
+   objIDs are (oid_text, oid_off[n + 1]) as geohip_format_points takes them (bit 63 of oid_off[p]:
+   point p's objID is null); the selection set is s strings (set_text, set_off[s + 1]) in the same
+   layout, s == 0 = the empty trajIDSet.
+     selection: every point when s == 0, else the points whose objID bytes equal a set string's
+                (String.equals); a null objID is in no set.  A null objID with s == 0 is the
+                reference's keyBy of a null key, where Flink throws: GEOHIP_ERR_ARG.
+     grouping:  trajectory t = the t-th distinct selected objID in order of first appearance (the
+                reference's order across keys is unspecified); inside a trajectory the points keep
+                arrival order = ascending index, as the window function sees them.
+   Outputs (device): traj_of[n] = each point's trajectory, 0xffffffff where not selected;
+   traj_first[T] = the index of each trajectory's first point (it names the objID); traj_off[T + 1];
+   perm = the selected point indices grouped by trajectory, ascending inside each (trajectory t =
+   perm[traj_off[t] .. traj_off[t + 1])).  perm needs n entries (n_sel are written), traj_first
+   cap_traj and traj_off cap_traj + 1.  *n_traj = T and *n_sel (host) are set when the call
+   returns; the arrays are ordered on the ctx stream.  GEOHIP_ERR_CAPACITY when cap_traj < T
+   (*n_traj = T, traj_first / traj_off / perm untouched).  Device memory only; n, s <= 2^30. */
+int geohip_traj_group(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oid_off, uint64_t n,
+                      const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint32_t* traj_of,
+                      uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm, uint64_t cap_traj,
+                      uint64_t* n_traj, uint64_t* n_sel);
+/* Windowed PointTStatsQuery: TStatsQueryWFunction.apply (tStats/TStatsQuery.java:148-189) per
+   trajectory of a geohip_traj_group result over the window's x / y / ts (n entries each):
+     last = 0, S = 0.0, T = 0; for each point in arrival order:
+       last == 0 (a test of the value, so it can hold again later): last = ts, (lx, ly) = (x, y), S = 0.0, T = 0
+       else if ts > last: S += sqrt((y-ly)*(y-ly) + (x-lx)*(x-lx))  (DistanceFunctions.java:60-63),
+                          T += ts - last (a Java long: wraps), last = ts, (lx, ly) = (x, y)
+   out_spatial[t] = S (the additions in arrival order), out_temporal[t] = T, out_avg[t] =
+   S / (double)T (NaN for 0.0 / 0, +-Infinity for S / 0).  GEOHIP_ERR_ARG when a perm entry is
+   >= n or traj_off is not ascending within n_sel (no such point is read).  Device memory only. */
+int geohip_tstats(geohip_ctx* ctx, const double* x, const double* y, const int64_t* ts, uint64_t n,
+                  const uint32_t* perm, uint64_t n_sel, const uint32_t* traj_off, uint64_t n_traj,
+                  double* out_spatial, int64_t* out_temporal, double* out_avg);
+/* out_x[j] = x[perm[j]], out_y likewise, out_ts too when ts is not NULL, for j < m: with traj_off
+   the windowed PointTFilterQuery's coordinate list per key (PointTFilterQuery.java:100-118; a
+   one-point key too -- its LineString is built without geometry, LineString.java:93-95).  The
+   real-time form (PointTFilterQuery.java:62-73) is the points with traj_of != 0xffffffff in
+   arrival order (geohip_traj_selected).  GEOHIP_ERR_ARG when a perm entry is >= n.  Device memory
+   only. */
+int geohip_traj_gather(geohip_ctx* ctx, const double* x, const double* y, const int64_t* ts, uint64_t n,
+                       const uint32_t* perm, uint64_t m, double* out_x, double* out_y, int64_t* out_ts);
+/* Real-time PointTFilterQuery (PointTFilterQuery.java:62-73): out_idx = the indices i with
+   traj_of[i] != 0xffffffff, ascending (n entries of room; *out_count, host, are written).  Device
+   memory only. */
+int geohip_traj_selected(geohip_ctx* ctx, const uint32_t* traj_of, uint64_t n, uint32_t* out_idx,
+                         uint64_t* out_count);
 
 /* ---- host-side planning introspection (no device needed) ------------------------------ */
 /* Query-cell sets of a point query as rectangles: point in G iff in any g rect; point in C

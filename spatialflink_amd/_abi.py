@@ -103,6 +103,22 @@ def oid_spans_to_strings(text: bytes, spans) -> list:
     return out
 
 
+def pack_strings(strings):
+    """Host (text uint8, off uint64 [m + 1]) of a list of str / bytes / None in the (oid_text, oid_off)
+    layout of geohip_format_points and geohip_traj_group: UTF-8 bytes concatenated, bit 63 of off[i]
+    set where entry i is None."""
+    off = np.zeros(len(strings) + 1, dtype=np.uint64)
+    parts, pos = [], 0
+    for i, v in enumerate(strings):
+        off[i] = pos | ((1 << 63) if v is None else 0)
+        if v is not None:
+            b = v if isinstance(v, (bytes, bytearray)) else str(v).encode("utf-8")
+            parts.append(bytes(b))
+            pos += len(b)
+    off[len(strings)] = pos
+    return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), off
+
+
 class CsvOutSpec(ctypes.Structure):
     """geohip_csv_out_spec: csvTsvSchemaAttr positions of objID, ts, x, y and the delimiter."""
     _fields_ = [("attr_oid", c_int32), ("attr_ts", c_int32), ("attr_x", c_int32), ("attr_y", c_int32),
@@ -243,6 +259,13 @@ _SIGS = {
     "geohip_ingest_trajectory": (c_int, [_P, POINTER(Grid), POINTER(IngestSpec), POINTER(TrajSpec), _P, c_uint64, _P,
                                          _P, _P, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
     "geohip_ingest_oid_compact": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, POINTER(c_uint64)]),
+    "geohip_traj_group": (c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64, POINTER(c_uint64),
+                                  POINTER(c_uint64)]),
+    "geohip_debug_traj_group_masked": (c_int, [_P, c_uint64, _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64,
+                                               POINTER(c_uint64), POINTER(c_uint64)]),
+    "geohip_tstats": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
+    "geohip_traj_gather": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
+    "geohip_traj_selected": (c_int, [_P, _P, c_uint64, _P, POINTER(c_uint64)]),
     "geohip_debug_selftest_fp64": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, _P]),
     "geohip_debug_classify": (c_int, [POINTER(Grid), c_double, c_double, c_double, _P, _P, c_uint64, _P]),
     "geohip_debug_knn_pass_stats": (c_int, [_P, _P]),
@@ -1049,6 +1072,112 @@ class Context:
                                            ln.value, off.data_ptr(), ctypes.byref(ln))
         self._check(rc, "ingest_oid_compact")
         return out[:ln.value], off
+
+    # ---- trajectory queries keyed by objID ------------------------------------------------
+    def traj_group(self, oid_text, oid_off, set_text=None, set_off=None, cap_traj=None, hash_mask=None):
+        """geohip_traj_group (device tensors: oid_text uint8, oid_off int64 [n + 1] with bit 63 = null,
+        as ingest_oid_compact returns them; the trajIDSet as (set_text, set_off) in the same layout, None
+        = empty): keyBy(objID) over the selected points.  Returns dict(traj_of int32 [n] (-1 = not
+        selected), traj_first int32 [T], traj_off int32 [T + 1], perm int32 [n_sel], n_traj, n_sel);
+        trajectory t = the t-th distinct selected objID by first appearance.  ``hash_mask``: the
+        geohip_debug_traj_group_masked test hook."""
+        import torch
+        self._dev(oid_off, "oid_off", "int64")
+        n = oid_off.numel() - 1
+        if n < 0:
+            raise GeohipArgumentError("traj_group: oid_off needs n + 1 entries")
+        self._dev(oid_text, "oid_text", "uint8")
+        if (set_text is None) != (set_off is None):
+            raise GeohipArgumentError("set_text and set_off go together")
+        s = 0
+        if set_off is not None:
+            self._dev(set_text, "set_text", "uint8")
+            self._dev(set_off, "set_off", "int64")
+            s = set_off.numel() - 1
+            if s < 0:
+                raise GeohipArgumentError("traj_group: set_off needs s + 1 entries")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        cap = n if cap_traj is None else int(cap_traj)
+        mk = lambda m: torch.empty(max(m, 1), dtype=torch.int32, device=oid_off.device)  # noqa: E731
+        traj_of, first, off, perm = mk(n), mk(cap), mk(cap + 1), mk(n)
+        nt, ns = c_uint64(0), c_uint64(0)
+        args = (oid_text.data_ptr(), oid_off.data_ptr(), n, set_text.data_ptr() if s else None,
+                set_off.data_ptr() if s else None, s, traj_of.data_ptr(), first.data_ptr(), off.data_ptr(),
+                perm.data_ptr(), cap, ctypes.byref(nt), ctypes.byref(ns))
+        if hash_mask is None:
+            rc = lib.geohip_traj_group(self.h, *args)
+        else:
+            rc = lib.geohip_debug_traj_group_masked(self.h, int(hash_mask), *args)
+        if rc == ERR_CAPACITY:
+            err = GeohipCapacityError(f"traj_group: {lib.geohip_last_error(self.h).decode(errors='replace')}")
+            err.n_traj = nt.value
+            raise err
+        self._check(rc, "traj_group")
+        T = nt.value
+        return {"traj_of": traj_of[:n], "traj_first": first[:T], "traj_off": off[:T + 1], "perm": perm[:ns.value],
+                "n_traj": T, "n_sel": ns.value}
+
+    def tstats(self, x, y, ts, perm, traj_off):
+        """geohip_tstats (device tensors; perm / traj_off of traj_group): per trajectory
+        (spatialLength float64, temporalLength int64, avgSpeed float64) of TStatsQueryWFunction."""
+        import torch
+        self._dev(x, "x")
+        self._dev(y, "y")
+        self._dev(ts, "ts", "int64")
+        self._dev(perm, "perm", "int32")
+        self._dev(traj_off, "traj_off", "int32")
+        n, T = x.numel(), traj_off.numel() - 1
+        if y.numel() != n or ts.numel() != n:
+            raise GeohipArgumentError("tstats: x, y and ts differ in length")
+        if T < 0:
+            raise GeohipArgumentError("tstats: traj_off needs T + 1 entries")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        sp = torch.empty(max(T, 1), dtype=torch.float64, device=x.device)
+        tl = torch.empty(max(T, 1), dtype=torch.int64, device=x.device)
+        av = torch.empty(max(T, 1), dtype=torch.float64, device=x.device)
+        rc = lib.geohip_tstats(self.h, x.data_ptr(), y.data_ptr(), ts.data_ptr(), n, perm.data_ptr(), perm.numel(),
+                               traj_off.data_ptr(), T, sp.data_ptr(), tl.data_ptr(), av.data_ptr())
+        self._check(rc, "tstats")
+        return sp[:T], tl[:T], av[:T]
+
+    def traj_gather(self, x, y, perm, ts=None):
+        """geohip_traj_gather: (x[perm], y[perm][, ts[perm]]) -- with traj_off the windowed TFilter's
+        coordinate lists."""
+        import torch
+        self._dev(x, "x")
+        self._dev(y, "y")
+        self._dev(perm, "perm", "int32")
+        n, m = x.numel(), perm.numel()
+        if y.numel() != n or (ts is not None and ts.numel() != n):
+            raise GeohipArgumentError("traj_gather: x, y and ts differ in length")
+        if ts is not None:
+            self._dev(ts, "ts", "int64")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        ox = torch.empty(max(m, 1), dtype=torch.float64, device=x.device)
+        oy = torch.empty_like(ox)
+        ot = torch.empty(max(m, 1), dtype=torch.int64, device=x.device) if ts is not None else None
+        rc = lib.geohip_traj_gather(self.h, x.data_ptr(), y.data_ptr(), ts.data_ptr() if ts is not None else None, n,
+                                    perm.data_ptr(), m, ox.data_ptr(), oy.data_ptr(),
+                                    ot.data_ptr() if ot is not None else None)
+        self._check(rc, "traj_gather")
+        return (ox[:m], oy[:m]) if ts is None else (ox[:m], oy[:m], ot[:m])
+
+    def traj_selected(self, traj_of):
+        """geohip_traj_selected: the selected points' indices (traj_of != -1), ascending -- the
+        real-time TFilter result."""
+        import torch
+        self._dev(traj_of, "traj_of", "int32")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        n = traj_of.numel()
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=traj_of.device)
+        cnt = c_uint64(0)
+        rc = lib.geohip_traj_selected(self.h, traj_of.data_ptr(), n, out.data_ptr(), ctypes.byref(cnt))
+        self._check(rc, "traj_selected")
+        return out[:cnt.value]
 
     def synth_uniform_async(self, x, y, base, seed, bbox):
         self._dev(x, "x")

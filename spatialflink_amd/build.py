@@ -34,6 +34,7 @@ SOURCES = {
     "band.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "format.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "sort.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
+    "traj.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
 }
 
 

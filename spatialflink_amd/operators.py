@@ -13,6 +13,8 @@ MI355X through libgeohip:
 ``PointPointKNNQuery.run``            ``spatialOperators/knn/PointPointKNNQuery.java:33-191``
 ``PointPointJoinQuery.run``           ``spatialOperators/join/PointPointJoinQuery.java:24-172``
 ``PointPolygonRangeQuery.run``        ``spatialOperators/range/PointPolygonRangeQuery.java:30-128``
+``PointTStatsQuery.run`` (window)     ``spatialOperators/tStats/PointTStatsQuery.java:64-92``, ``TStatsQuery.java:148-189``
+``PointTFilterQuery.run``             ``spatialOperators/tFilter/PointTFilterQuery.java:30-118``
 ====================================  =========================================================
 
 Window contents are columnar (``PointWindow``: x, y and optional object ids); results are
@@ -251,6 +253,90 @@ class PointPolygonRangeQuery(_Operator):
         pr, off, vx, vy = _rings(polys)
         return self._ctx().range_ppoly(self.index.abi(), window.x, window.y, off, vx, vy, float(query_radius),
                                        self.conf.approximate_query, poly_rings=pr)
+
+
+@dataclass
+class TrajectoryWindow:
+    """One window of a TrajectoryStream, columnar on the device: x, y float64, ts int64
+    (timeStampMillisec) and the objIDs as (oid_text uint8, oid_off int64 [n + 1], bit 63 = null) --
+    what ``Context.ingest_trajectory`` + ``ingest_oid_compact`` produce."""
+    x: object
+    y: object
+    ts: object
+    oid_text: object
+    oid_off: object
+
+    def __len__(self):
+        return len(self.x)
+
+    @classmethod
+    def from_host(cls, x, y, ts, obj_ids, device="cuda:0") -> "TrajectoryWindow":
+        """From host columns and a list of str / None objIDs (tests, small windows)."""
+        import torch
+        text, off = _abi.pack_strings(list(obj_ids))
+        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)  # noqa: E731
+        return cls(dev(x, np.float64), dev(y, np.float64), dev(ts, np.int64), dev(text, np.uint8),
+                   dev(off.view(np.int64), np.int64))
+
+
+class _TrajOperator(_Operator):
+    """The trajectory operators take (conf, index) like the others; the grid is not read."""
+
+    def __init__(self, conf: QueryConfiguration, index: Optional[UniformGrid] = None,
+                 ctx: Optional[_abi.Context] = None):
+        super().__init__(conf, index, ctx)
+
+    def _group(self, window: TrajectoryWindow, traj_id_set):
+        """keyBy(objID) of the points the trajIDSet filter keeps (PointTStatsQuery.java:76-92)."""
+        import torch
+        ids = sorted(traj_id_set) if traj_id_set else []
+        st = so = None
+        if ids:
+            text, off = _abi.pack_strings(ids)
+            dev = window.oid_off.device
+            st = torch.from_numpy(text).to(dev)
+            so = torch.from_numpy(off.view(np.int64)).to(dev)
+        return self._ctx().traj_group(window.oid_text, window.oid_off, st, so)
+
+    @staticmethod
+    def _obj_ids(window: TrajectoryWindow, first) -> list:
+        """The objID string of each trajectory (its first point's)."""
+        off = window.oid_off.cpu().numpy().view(np.uint64)
+        text = window.oid_text.cpu().numpy().tobytes()
+        m = (1 << 63) - 1
+        return [text[int(off[i]) & m:int(off[i + 1]) & m].decode("utf-8", "replace") for i in first.cpu().tolist()]
+
+
+class PointTStatsQuery(_TrajOperator):
+    """PointTStatsQuery.run, window branch (tStats/PointTStatsQuery.java:64-92 +
+    TStatsQuery.java:148-189): per selected trajectory (objID, spatialLength, temporalLength,
+    avgSpeed = spatialLength / temporalLength), in order of the objIDs' first appearance."""
+
+    def run(self, window: TrajectoryWindow, traj_id_set=()):
+        if self.conf.query_type != QueryType.WindowBased:
+            raise _abi.GeohipUnsupportedError("PointTStatsQuery: only the WindowBased form is evaluated here")
+        g = self._group(window, traj_id_set)
+        sp, tl, av = self._ctx().tstats(window.x, window.y, window.ts, g["perm"], g["traj_off"])
+        return list(zip(self._obj_ids(window, g["traj_first"]), sp.cpu().tolist(), tl.cpu().tolist(), av.cpu().tolist()))
+
+
+class PointTFilterQuery(_TrajOperator):
+    """PointTFilterQuery.run (tFilter/PointTFilterQuery.java:30-118).  RealTime (:62-73): the
+    selected points' window indices in arrival order.  WindowBased (:100-118): per selected
+    trajectory (objID, coords [k, 2]) in arrival order, one-point trajectories included (the
+    reference emits them as a LineString without geometry, LineString.java:93-95), trajectories in
+    order of first appearance."""
+
+    def run(self, window: TrajectoryWindow, traj_id_set=()):
+        self._check_type()
+        g = self._group(window, traj_id_set)
+        if self.conf.query_type == QueryType.RealTime:
+            return self._ctx().traj_selected(g["traj_of"])
+        gx, gy = self._ctx().traj_gather(window.x, window.y, g["perm"])
+        xy = np.stack([gx.cpu().numpy(), gy.cpu().numpy()], axis=1) if g["n_sel"] else np.zeros((0, 2))
+        off = g["traj_off"].cpu().tolist()
+        ids = self._obj_ids(window, g["traj_first"])
+        return [(ids[t], xy[off[t]:off[t + 1]]) for t in range(g["n_traj"])]
 
 
 def _rings(polys):

@@ -142,6 +142,47 @@ def _digits(v: np.ndarray, width: int) -> np.ndarray:
     return ((v[:, None] // p[None, :]) % 10 + 48).astype(np.uint8)
 
 
+def trajectories(n: int, n_traj: int, seed: int, bbox=BEIJING, ts0: int = 1611022449423, step_ms: int = 100,
+                 out_of_order: float = 0.05, sigma: float = 1e-4, prefix: str = "veh-"):
+    """A TrajectoryStream window on the host (tests, scripts/traj_step.py): n points of n_traj
+    trajectories in interleaved arrival order (point i belongs to a random trajectory; with
+    n >= n_traj every trajectory occurs), each trajectory a Gaussian random walk (step sigma) from a
+    uniform start in bbox, objIDs ``veh-<k>``, timestamps ts0 + i * step_ms except that a share
+    ``out_of_order`` of the points arrives up to 50 steps late (a smaller timestamp than its
+    predecessors').  Returns dict(x, y float64; ts int64; traj int64 [n] = k per point; oid_text uint8,
+    oid_off uint64 [n + 1]: the objIDs in the (oid_text, oid_off) layout of the output codecs)."""
+    rng = np.random.default_rng(seed)
+    k = rng.integers(0, max(n_traj, 1), n, dtype=np.int64)
+    if n >= n_traj:
+        k[:n_traj] = rng.permutation(n_traj)
+    min_x, max_x, min_y, max_y = bbox
+    sx = rng.uniform(min_x, max_x, max(n_traj, 1))
+    sy = rng.uniform(min_y, max_y, max(n_traj, 1))
+    order = np.argsort(k, kind="stable")  # a trajectory's points, in arrival order
+    ks = k[order]
+    starts = np.flatnonzero(np.r_[True, ks[1:] != ks[:-1]]) if n else np.zeros(0, np.int64)
+    x, y = np.empty(n), np.empty(n)
+    for out, s0 in ((x, sx), (y, sy)):
+        steps = rng.normal(0.0, sigma, n)
+        steps[starts] = 0.0
+        walk = np.cumsum(steps)
+        base = np.repeat(walk[starts], np.diff(np.r_[starts, n])) if n else walk
+        out[order] = s0[ks] + (walk - base)
+    ts = ts0 + np.arange(n, dtype=np.int64) * step_ms
+    late = rng.random(n) < out_of_order
+    ts[late] -= rng.integers(1, 51, int(late.sum()), dtype=np.int64) * step_ms
+    width = len(str(max(n_traj - 1, 0)))
+    dig = _digits(k, width)
+    keep = np.cumsum(dig != 48, axis=1) > 0
+    keep[:, -1] = True
+    pre = np.frombuffer(prefix.encode(), dtype=np.uint8)
+    mat = np.hstack([np.broadcast_to(pre, (n, len(pre))), dig])
+    keep = np.hstack([np.ones((n, len(pre)), bool), keep])
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(keep.sum(axis=1))
+    return {"x": x, "y": y, "ts": ts, "traj": k, "oid_text": mat[keep], "oid_off": off}
+
+
 def csv_text(n: int, seed: int, bbox=BEIJING, frac_digits: int = 13, ts0: int = 1611022449423,
              chunk: int = 1 << 20):
     """CSVTSVToTSpatial records "oid,ts,x,y\\n" (csvTsvSchemaAttr [0, 1, 2, 3]) for the uniform
