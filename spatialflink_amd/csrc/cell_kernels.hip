@@ -1717,7 +1717,48 @@ __device__ __forceinline__ void two_sum(double a, double b, double& s, double& e
     e = (a - av) + (b - bv);
 }
 
+// fma(a, b, -fl(a b)) is the product's rounding error only while that error is representable and
+// nothing overflowed: |a b| in [2^-960, 2^1020], or an exact zero.
+__device__ __forceinline__ bool product_error_free(double a, double b, double p) {
+    const double ap = __builtin_fabs(p);
+    return (ap >= 0x1.0p-960 && ap <= 0x1.0p1020) || a == 0.0 || b == 0.0;
+}
+__device__ __forceinline__ int exact_det_sign_normal(double x1, double y1, double x2, double y2);
+
+// The same sign when a product leaves that range (finite operands): with v = m_v 2^e_v (frexp,
+// |m_v| in [1/2, 1)) the products are (m_x1 m_y2) 2^(a + b) and (m_y1 m_x2) 2^(c + d), the
+// mantissa products in [1/4, 1).  Different signs or an exponent gap of 3 decide; otherwise one
+// operand takes the gap (an exact scaling by at most 4) and the expansion runs on the mantissas,
+// whose products and residuals are normal.  RobustDeterminant forms no product at all, so its
+// answer is the exact sign whatever the magnitudes.
+__device__ __noinline__ int exact_det_sign_scaled(double x1, double y1, double x2, double y2) {
+    int a, b, c, d;
+    double mx1 = __builtin_frexp(x1, &a);
+    const double my2 = __builtin_frexp(y2, &b);
+    double my1 = __builtin_frexp(y1, &c);
+    const double mx2 = __builtin_frexp(x2, &d);
+    const double mp = mx1 * my2, mq = my1 * mx2;
+    const int sp = (mp > 0.0) - (mp < 0.0), sq = (mq > 0.0) - (mq < 0.0);
+    if (sp != sq) return sp > sq ? 1 : -1;
+    if (sp == 0) return 0;
+    const int de = (a + b) - (c + d);
+    if (de >= 3) return sp;
+    if (de <= -3) return -sp;
+    if (de >= 0) mx1 = __builtin_ldexp(mx1, de);
+    else my1 = __builtin_ldexp(my1, -de);
+    return exact_det_sign_normal(mx1, my1, mx2, my2);
+}
+
 __device__ __forceinline__ int exact_det_sign(double x1, double y1, double x2, double y2) {
+    const double p0 = x1 * y2, q0 = y1 * x2;
+    if (!(product_error_free(x1, y2, p0) && product_error_free(y1, x2, q0)) &&
+        __builtin_fabs(x1) <= kDblMax && __builtin_fabs(y1) <= kDblMax && __builtin_fabs(x2) <= kDblMax &&
+        __builtin_fabs(y2) <= kDblMax)
+        return exact_det_sign_scaled(x1, y1, x2, y2);
+    return exact_det_sign_normal(x1, y1, x2, y2);
+}
+
+__device__ __forceinline__ int exact_det_sign_normal(double x1, double y1, double x2, double y2) {
     const double p = x1 * y2;
     const double ep = __builtin_fma(x1, y2, -p);
     const double q = y1 * x2;
@@ -1852,7 +1893,10 @@ __device__ __forceinline__ double screen_lim2(double px, double py, const double
     const double m = ((__builtin_fabs(px - bb[0]) + __builtin_fabs(py - bb[1])) +
                       2.0 * ((bb[2] - bb[0]) + (bb[3] - bb[1])) + __builtin_fabs(r)) * 0x1.0p-44;
     const double lim = r + m;
-    return lim * lim;
+    // a square below 2^-900 is compared against sums of subnormal squares, whose rounding is
+    // absolute (not within the relative margin): no bound then, nothing is rejected
+    const double l2 = lim * lim;
+    return l2 >= 0x1.0p-900 ? l2 : __builtin_inf();
 }
 __device__ __forceinline__ double box_dist2(double px, double py, double x0, double y0, double x1, double y1) {
     const double ex = __builtin_fmax(__builtin_fmax(x0 - px, px - x1), 0.0);
@@ -1904,10 +1948,12 @@ __device__ __forceinline__ bool segment_within(double px, double py, double ax, 
     // (M = |p-A|_1 + |B-A|_1), so each computed quantity is within 2^-50 M^2 of its value: E =
     // 2^-45 M^2 covers it, and the (1 -/+ 2^-45) factors cover the roundings of the squared
     // bounds.  NaN or an infinity anywhere fails every decision (the exact path runs).
-    {
-        const double dax = px - ax, day = py - ay, dbx = px - bx, dby = py - by;
-        const double ex = bx - ax, ey = by - ay;
-        const double M = __builtin_fabs(dax) + __builtin_fabs(day) + __builtin_fabs(ex) + __builtin_fabs(ey);
+    // Below M^2 = 2^-900 the products are subnormal (absolute, not relative, rounding): no screen.
+    const double dax = px - ax, day = py - ay;
+    const double ex = bx - ax, ey = by - ay;
+    const double M = __builtin_fabs(dax) + __builtin_fabs(day) + __builtin_fabs(ex) + __builtin_fabs(ey);
+    if (M * M >= 0x1.0p-900) {
+        const double dbx = px - bx, dby = py - by;
         const double E = M * M * 0x1.0p-45;
         const double dl = M * 0x1.0p-48 + __builtin_fabs(r) * 0x1.0p-49;
         const double rl = r - dl, rh = r + dl;
@@ -1971,7 +2017,11 @@ __device__ __forceinline__ Fp32Screen fp32_screen(double px, double py, const do
     const double ext = (gb[2] - gb[0]) + (gb[3] - gb[1]);
     const double S = (__builtin_fabs(u) + __builtin_fabs(v) + ext) * 0x1.0p-18 + 0x1.0p-100;
     const double ls = __builtin_sqrt(lim2) * (1.0 + 0x1.0p-40) + S;
-    return Fp32Screen{(float)u, (float)v, (float)(ls * ls * (1.0 + 0x1.0p-19))};
+    // The 2^-22 rounding bound of the fp32 squares holds for normal fp32 values only: a bound
+    // below 2^-100 (fp32 squares there may be subnormal: absolute, not relative, rounding) never
+    // rejects.  Above it every sum that exceeds the bound is normal.
+    const double b2 = ls * ls * (1.0 + 0x1.0p-19);
+    return Fp32Screen{(float)u, (float)v, b2 >= 0x1.0p-100 ? (float)b2 : __builtin_inff()};
 }
 
 // JTS DistanceOp(point, polygon) predicate "distance <= r" (r < MAX_VALUE):
@@ -4909,6 +4959,11 @@ bool classify_cells(const PolyDev& P, const std::vector<double>& hvx, const std:
         bc.segs.push_back(cls::Seg{ax, ay, bx, by, rid ? (uint32_t)rid[i] : 0u});
     }
     if (bc.segs.empty()) return false;
+    // The classifier's margins are relative: they cover its own roundings only while the squares
+    // of the region's lengths are normal doubles.  Outside that range no cell is classified and
+    // every point takes the exact per-point path.
+    const double ext = (P.gb[2] - P.gb[0]) + (P.gb[3] - P.gb[1]) + r + pg.cell_len;
+    if (!(ext * ext >= 0x1.0p-700 && ext * ext <= 0x1.0p1010)) return false;
     const int32_t w = P.wx1 - P.wx0 + 1, h = P.wy1 - P.wy0 + 1;
     if ((uint64_t)w * (uint64_t)h * bc.segs.size() > 8000000ull) return false;
     std::vector<double> xl(w), xh(w), yl(h), yh(h);
