@@ -535,7 +535,7 @@ __host__ __device__ inline bool json_string_end(const R& rd, uint64_t p, uint64_
     *esc = false;
     for (p++;; p++) {
         const uint8_t c = rd(p);
-        if (c == '\n') return false;
+        if (c < 0x20) return false;  // '\n' ends the record; Jackson rejects any unescaped control character
         if (c == '"') break;
         if (c == '\\') {
             *esc = true;

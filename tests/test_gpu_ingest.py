@@ -164,13 +164,15 @@ def test_geojson(ctx):
 
 
 def test_tiny_records_dense_chunks(ctx):
-    # 4-byte records: 2048 records per 8 KB chunk, every lane parses 8 records
+    # 4-byte records: 6144 record starts per 24 KB chunk, more than the hot kernel lists (kFastStarts
+    # = 4096), so every chunk goes whole to ingest_general (test_gpu_ingest_numeric.py runs the hot
+    # kernel's multi-round loop)
     text = b"\n".join(b"%d,%d" % (i % 10, (i * 7) % 10) for i in range(200000))
     assert _check(ctx, cref.CSV, text, fx=0, fy=1, fts=-1) == 200000
 
 
 def test_long_records_straddle_chunks(ctx):
-    # records longer than the 4 KB LDS tail: the parser reads past the staged window from HBM
+    # records longer than the 512-byte LDS tail: the parser reads past the staged window from HBM
     rng = random.Random(6)
     lines = []
     for i in range(400):

@@ -3,7 +3,9 @@
 The device record parser (spatialflink_amd/csrc/ingest_parse.h) is __host__ __device__ code;
 ``_abi.debug_ingest_record`` runs the same functions host-compiled, so these tests check its
 decisions without a GPU.  The kernels that split a batch into records and run the parser per
-lane are checked on the GPU by tests/test_gpu_ingest.py.
+lane are checked on the GPU by tests/test_gpu_ingest.py, and tests/test_gpu_ingest_numeric.py
+runs these same cases through them: the known answers and the fuzz generators live in
+tests/ingest_cases.py, shared by both.
 
 Known answers are derived by hand from the Java code (paths relative to
 /root/reference/src/main/java/GeoFlink): CSVTSVToSpatial / CSVTSVToTSpatial
@@ -20,7 +22,6 @@ import struct
 import sys
 from pathlib import Path
 
-import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -30,99 +31,10 @@ sys.path.insert(0, str(ROOT / "oracle"))
 import cref  # noqa: E402  (oracle: the checker)
 from spatialflink_amd import _abi  # noqa: E402
 
-NAN = float("nan")
-INF = float("inf")
+from ingest_cases import (CSV, KNOWN, TSV, WKT, _rand_decimal, halfway_tokens, halfway_values,  # noqa: E402
+                          hex_or_long_exponent_token)
 
-# ATC-style CSVTSVToTSpatial schema: [oid, ts, x, y] -> csvTsvSchemaAttr = [0, 1, 2, 3]
-CSV_T = ("csv", ",", 2, 3, 1)
-CSV = ("csv", ",", 2, 3, -1)
-TSV = ("csv", "\t", 0, 1, -1)
-WKT = ("wkt", ",", 0, 1, -1)
-GEO = ("geojson", ",", 0, 1, -1)
 _FMT = {"csv": cref.CSV, "geojson": cref.GEOJSON, "wkt": cref.WKT}
-
-# (spec, record, expected (x, y, ts) or None where the reference throws, device-may-reject)
-# device-may-reject: valid Java input outside the device grammar (the batch call then returns
-# GEOHIP_ERR_UNSUPPORTED and the caller hands the batch to the reference deserializer).
-KNOWN = [
-    (CSV_T, b"7,1611022449423,116.4148990000001,39.92037412345", (116.4148990000001, 39.92037412345, 1611022449423), False),
-    (CSV_T, b'"7","1611022449423","116.5","39.75"', (116.5, 39.75, 1611022449423), False),
-    (CSV_T, b"7 , 12 , 116.5 , 39.75", (116.5, 39.75, 12), False),
-    (CSV_T, b"7,12,116.5", None, False),  # get(3): IndexOutOfBoundsException
-    (CSV_T, b"7,12,116.5,abc", None, False),  # NumberFormatException
-    (CSV_T, b"7,12,1e3,-2.5E-1", (1000.0, -0.25, 12), False),
-    (CSV_T, b"7,12,+1.5d,2f", (1.5, 2.0, 12), False),  # Java type suffixes
-    (CSV_T, b"7,12,NaN,-Infinity", (NAN, -INF, 12), False),
-    (CSV_T, b"7,12,.5,5.", (0.5, 5.0, 12), False),
-    (CSV_T, b"7,12,.,1", None, False),
-    (CSV_T, b"7,12,1e,1", None, False),
-    (CSV_T, b"7,12,nan,1", None, False),  # NaN is case-sensitive
-    (CSV_T, b"7,12,1.5\x01,2", (1.5, 2.0, 12), False),  # Double.valueOf trims every char <= ' '
-    (CSV_T, b"7,+12,1,2", (1.0, 2.0, 12), False),
-    (CSV_T, b"7,12.0,1,2", None, False),  # Long.valueOf
-    (CSV_T, b"7, 12\x01,1,2", None, False),  # Long.valueOf does not trim
-    (CSV_T, b"7,9223372036854775808,1,2", None, False),  # Long overflow
-    (CSV_T, b"7,-9223372036854775808,1,2", (1.0, 2.0, -9223372036854775808), False),
-    (CSV_T, b"7,9223372036854775807,1,2", (1.0, 2.0, 9223372036854775807), False),
-    (CSV_T, b"7,12,0x1.8p1,2", (3.0, 2.0, 12), False),  # hex significand
-    (CSV_T, b"7,12,-0X.8P-1d,0x1p-1074", (-0.25, 5e-324, 12), False),
-    (CSV_T, b"7,12,0x1p-1075,0x1.0000000000001p-1075", (0.0, 5e-324, 12), False),  # tie to even / just above
-    (CSV_T, b"7,12,0x1.fffffffffffff8p1023,0x1p99999999999", (INF, INF, 12), False),  # rounds past MAX / int range
-    (CSV_T, b"7,12,0x0.0p5,-0x1p-99999999999", (0.0, -0.0, 12), False),
-    (CSV_T, b"7,12,0x1.00000000000008p0,0x1.00000000000018p0", (1.0, 1.0000000000000004, 12), False),  # ties
-    (CSV_T, b"7,12,0x123456789abcdef0123p-70,2", (float.fromhex("0x123456789abcdef0123p-70"), 2.0, 12), False),
-    (CSV_T, b"7,12,0xp1,2", None, False),
-    (CSV_T, b"7,12,0x1.8p,2", None, False),
-    (CSV_T, b"7,12,0x1.8,2", None, False),  # hex needs a binary exponent
-    (CSV_T, b"7,12,1.5,2,extra", (1.5, 2.0, 12), False),
-    (CSV_T, b",12,1,2", (1.0, 2.0, 12), False),  # leading "" field
-    (CSV_T, b"7,12,0.1,0.30000000000000004", (0.1, 0.30000000000000004, 12), False),
-    (CSV_T, b"7,12,9007199254740993,2", (9007199254740992.0, 2.0, 12), False),  # tie -> even
-    (CSV_T, b"7,12,1.000000000000000000000001,2", (1.0, 2.0, 12), False),  # 25 digits, decided by truncation
-    (CSV_T, b"7,12,2.2250738585072011e-308,4.9e-324", (2.225073858507201e-308, 5e-324, 12), False),
-    (CSV_T, b"7,12,1e400,1e-400", (INF, 0.0, 12), False),
-    (CSV_T, b"7,12,-0.0,0", (-0.0, 0.0, 12), False),
-    (CSV_T, b"7,12,1e1000000,2", (INF, 2.0, 12), False),  # 7-digit exponent
-    (CSV_T, b"7,12,1e-99999999999999,0e99999999999", (0.0, 0.0, 12), False),
-    (CSV_T, b"7,12,-0.001e1000000002,2", (-INF, 2.0, 12), False),
-    (CSV_T, b'7,12,1"5,2', (15.0, 2.0, 12), False),  # quotes deleted inside a token
-    (CSV_T, b'7,1"2,-"1".5"e1,2', (-15.0, 2.0, 12), False),
-    (CSV_T, b"7,12,1 5,2", None, False),
-    (CSV, b"a,b,116.5,39.75", (116.5, 39.75, 0), False),
-    (CSV, b"a,b,116.5,", None, False),  # trailing "" removed -> get(3) throws
-    (CSV, b"a,b,116.5,\t", None, False),
-    (TSV, b"116.5\t39.75", (116.5, 39.75, 0), False),
-    (TSV, b"116.5 \t 39.75", (116.5, 39.75, 0), False),
-    (TSV, b"116.5 39.75", None, False),  # no tab: one field
-    (TSV, b" 116.5\t39.75 ", (116.5, 39.75, 0), False),
-    (TSV, b'116.5"\t"39.75', (116.5, 39.75, 0), False),
-    (WKT, b"POINT (116.5 39.75)", (116.5, 39.75, 0), False),
-    (WKT, b"POINT(116.5 39.75)", (116.5, 39.75, 0), False),
-    (WKT, b"id,POINT ( 116.5   39.75 ) trailing", (116.5, 39.75, 0), False),
-    (WKT, b"POINT (116.5,39.75)", None, False),
-    (WKT, b"POINT EMPTY", None, False),
-    (WKT, b"MULTIPOINT ((1 2))", None, False),
-    (WKT, b"POINT (1 2 3)", (1.0, 2.0, 0), False),
-    (WKT, b"POINT (nan NaN 0x1p4)", (NAN, NAN, 0), False),  # WKTReader: NaN ignoring case
-    (WKT, b"POINT (1 2 3 4)", None, False),
-    (WKT, b"POINT (1 2 x)", None, False),
-    (WKT, b"POINT (1.5d -2e1)", (1.5, -20.0, 0), False),
-    (WKT, b"point (1 2)", None, False),
-    (WKT, b"POINTZ (1 2)", None, False),
-    (GEO, b'{"geometry":{"coordinates":[116.44412,39.93984],"type":"Point"},"properties":{"oID":"2560",'
-          b'"timestamp":"2008-02-02 20:12:32"},"type":"Feature"}', (116.44412, 39.93984, 0), False),
-    (GEO, b'{"type":"Point","coordinates":[1,2]}', (1.0, 2.0, 0), False),
-    (GEO, b'{"type":"Point","coordinates":[ -0 , 2.5e-1 ]}', (0.0, 0.25, 0), False),  # IntNode 0
-    (GEO, b'{"type":"Point","coordinates":[-0.0,1]}', (-0.0, 1.0, 0), False),
-    (GEO, b'{"type":"Point","coordinates":[01,2]}', None, False),
-    (GEO, b'{"type":"Point","coordinates":[+1,2]}', None, False),
-    (GEO, b'{"type":"Point","coordinates":[1.,2]}', None, False),
-    (GEO, b'{"type":"LineString","coordinates":[[1,2],[3,4]]}', (1.0, 2.0, 0), False),
-    (GEO, b'{"type":"Point","coordinates":[1e400,2]}', None, False),
-    (GEO, b'{"type":"Point","coordinates":[9223372036854775807,-9223372036854775808]}',
-     (9.223372036854776e18, -9.223372036854776e18, 0), False),  # LongNode
-    (GEO, b'{"type":"Point","coordinates":[9223372036854775808,1]}', None, False),  # BigIntegerNode
-]
 
 
 def _spec_oracle(s):
@@ -161,22 +73,6 @@ def test_device_parser_known_answers(spec, rec, want, may_reject):
         assert _same(got[0], want[0]) and _same(got[1], want[1]) and got[2] == want[2]
 
 
-def _rand_decimal(rng: random.Random) -> str:
-    nint = rng.choice([0, 1, 1, 2, 3, 5, 10, 17, 20])
-    nfrac = rng.choice([0, 1, 2, 5, 10, 13, 16, 17, 19, 22])
-    if nint + nfrac == 0:
-        nint = 1
-    ip = "".join(rng.choice("0123456789") for _ in range(nint))
-    fp = "".join(rng.choice("0123456789") for _ in range(nfrac))
-    s = ip + ("." + fp if nfrac or rng.random() < 0.1 else "")
-    if rng.random() < 0.4:
-        s += rng.choice("eE") + rng.choice(["", "+", "-"]) + str(rng.choice([0, 1, 5, 22, 23, 100, 290, 300, 307, 308,
-                                                                                  309, 320, 324, 330, 340, 350]))
-    if rng.random() < 0.3:
-        s = rng.choice("+-") + s
-    return s
-
-
 def test_decimal_conversion_fuzz():
     """Random decimal tokens: device parser == oracle == Python float (all correctly rounded)."""
     rng = random.Random(20260116)
@@ -202,23 +98,16 @@ def test_decimal_conversion_fuzz():
 def test_decimal_halfway_cases():
     """Points at (and 1e-35 relative around) the midpoint of adjacent doubles, written with 17-41
     significant digits: where the device parser decides, it matches Python's correctly rounded float."""
-    from decimal import Decimal, getcontext
-    getcontext().prec = 80
-    rng = np.random.default_rng(7)
     spec_d = _spec_dev(TSV)
-    vals = rng.uniform(-1e3, 1e3, 300).tolist() + [1.0, 0.1, 116.41, 39.92, 5e-324, 1e300, 2.0 ** -1022]
+    vals = halfway_values()
     decided = 0
-    for v in vals:
-        mid = (Decimal(v) + Decimal(float(np.nextafter(v, np.inf)))) / 2
-        for t in (mid, mid * (1 + Decimal(10) ** -35), mid * (1 - Decimal(10) ** -35)):
-            for digits in (16, 17, 20, 40):
-                s = format(t, f".{digits}e")
-                d = _abi.debug_ingest_record(spec_d, f"{s}\t1".encode())
-                if d is not None:
-                    decided += 1
-                    assert _same(d[0], float(s)), s
-                else:
-                    assert digits + 1 > 19, s
+    for s, digits in halfway_tokens(vals):
+        d = _abi.debug_ingest_record(spec_d, f"{s}\t1".encode())
+        if d is not None:
+            decided += 1
+            assert _same(d[0], float(s)), s
+        else:
+            assert digits + 1 > 19, s
     assert decided > len(vals) * 6
 
 
@@ -291,28 +180,7 @@ def test_hex_and_long_exponent_fuzz():
     rng = random.Random(424242)
     spec_d, spec_o = _spec_dev(TSV), _spec_oracle(TSV)
     for _ in range(20000):
-        toks = []
-        for _t in range(2):
-            if rng.random() < 0.7:
-                ih = "".join(rng.choice("0123456789abcdefABCDEF") for _ in range(rng.choice([0, 1, 2, 7, 14, 16, 20])))
-                fh = "".join(rng.choice("0123456789abcdef") for _ in range(rng.choice([0, 1, 3, 13, 15, 20])))
-                if not ih and not fh:
-                    ih = "1"
-                body = ih + ("." + fh if fh or rng.random() < 0.2 else "")
-                ex = rng.choice([0, 1, -1, 52, -1022, -1074, -1075, -1080, 1023, 1024, -1100, 900, -990,
-                                 rng.randint(-1200, 1200)])
-                t = rng.choice(["", "-", "+"]) + rng.choice(["0x", "0X"]) + body + rng.choice("pP") + str(ex)
-                t += rng.choice(["", "", "d", "F"])
-                try:
-                    want = float.fromhex(t.rstrip("dF"))
-                except OverflowError:
-                    want = -INF if t.startswith("-") else INF
-            else:
-                m = rng.choice(["1", "0", "0.0", "7.25", "123456789", "0.000001"])
-                e = rng.choice([1000000, 99999999, 123456789012, -1000000, -99999999999])
-                t = rng.choice(["", "-"]) + m + "e" + str(e)
-                want = float(t)
-            toks.append((t, want))
+        toks = [hex_or_long_exponent_token(rng), hex_or_long_exponent_token(rng)]
         rec = f"{toks[0][0]}\t{toks[1][0]}".encode()
         o = cref.ingest_record(spec_o, rec)
         d = _abi.debug_ingest_record(spec_d, rec)
