@@ -24,7 +24,10 @@
  *                         spatialOperators/tStats/PointTStatsQuery.java:76-92, tFilter/PointTFilterQuery.java:89-107
  *   geohip_tstats      <- TStatsQueryWFunction.apply                  spatialOperators/tStats/TStatsQuery.java:148-189
  *   geohip_traj_gather <- PointTFilterQuery's window function         spatialOperators/tFilter/PointTFilterQuery.java:100-118
- *   geohip_grid        <- UniformGrid getters                        spatialIndices/UniformGrid.java:136-146
+ *   geohip_trange_classify <- PointPolygonTRangeQuery's cell filter and contains test
+ *                         spatialOperators/tRange/PointPolygonTRangeQuery.java:55-81, 92-130
+ *   geohip_traj_filter_hit <- its window join back to the whole trajectories   :140-177
+ *   geohip_grid        <- UniformGrid getters                      spatialIndices/UniformGrid.java:136-146
  *                         (values copied from the Java object, so both constructors :47-85 are covered)
  *
  * Semantics (bit-exact contract, DESIGN.md "Parity"):
@@ -514,6 +517,56 @@ int geohip_traj_gather(geohip_ctx* ctx, const double* x, const double* y, const 
 int geohip_traj_selected(geohip_ctx* ctx, const uint32_t* traj_of, uint64_t n, uint32_t* out_idx,
                          uint64_t* out_count);
 
+/* ---- trajectory range query (PointPolygonTRangeQuery) ---------------------------------- */
+/* Per point of one window its class against a polygon set
+   (spatialOperators/tRange/PointPolygonTRangeQuery.java:53-87 real time, :90-177 window):
+     0  the point's cell (utils/HelperClass.java:104-120, not clipped to the grid) is in no
+        polygon's gridIDsSet (:55-59, 92-97; HelperClass.java:123-143: every cell of the bbox
+        corners' cell range, not clipped either) -- the filter of :62-71, 100-109 drops it;
+     1  the cell is in the set and no polygon contains the point;
+     2  the cell is in the set and some polygon contains it (:81, :130:
+        polygon.contains(point.getEnvelope())).
+   contains is JTS Geometry.contains, strict interior -- not the "distance <= r" of the range
+   and join calls, which counts the boundary: the polygon's envelope (its shell's) must cover
+   the point (a NaN coordinate fails) and PointLocator.locateInPolygon must say INTERIOR.  A
+   point on a shell edge or vertex, outside the shell, or on or inside a hole whose envelope
+   includes it is not contained.  Any polygon of the set may contain the point, whichever
+   polygon's cells let it pass the filter.  Cells are compared as integer pairs; the reference
+   compares "%05d%05d" strings, which is the same as long as every polygon cell index lies in
+   [-9999, 99999]: GEOHIP_ERR_ARG for a polygon whose bbox cell range leaves it, and where the
+   reference's bbox loop does not end (upper index INT_MAX).  A point's own index may be
+   anything; one that saturates matches no polygon cell.  One grid assigns the cells of points
+   and polygons; the reference also admits Point and Polygon objects built on different grids,
+   which this call does not cover.
+   Polygons (host memory, as geohip_range_ppoly takes them, built by createPolygon with the same
+   GEOHIP_ERR_ARG cases) are planned once and cached in the ctx until another set arrives.
+   x, y (n entries), out_class (n) and out_idx (cap) are device memory; *out_count is host.
+   out_idx receives the indices of class 2, ascending: the real-time form's output.
+   GEOHIP_ERR_CAPACITY with *out_count = the required size when cap is too small (the classes
+   are written all the same); out_idx == NULL with cap == 0 asks for the classes only.  npoly ==
+   0: every class is 0 and *out_count 0.  n <= 2^32 - 1.  Device memory only. */
+int geohip_trange_classify(geohip_ctx* ctx, const geohip_grid* grid, const double* x, const double* y, uint64_t n,
+                           const uint32_t* poly_rings /* nullable */, const uint32_t* ring_off, const double* vx,
+                           const double* vy, uint64_t nv, uint32_t npoly, uint8_t* out_class,
+                           uint32_t* out_idx /* nullable */, uint64_t cap, uint64_t* out_count);
+/* The trajectories of a geohip_traj_group result (traj_of[n], traj_first[n_traj], traj_off[n_traj
+   + 1], perm[n_sel]) that own a point i with cls[i] >= threshold, with all their points: the
+   window form (PointPolygonTRangeQuery.java:140-177 joins the contained points back to every
+   point of their objID; threshold 2 on geohip_trange_classify's classes).  The kept trajectories
+   are renumbered in their existing (first-appearance) order and their perm slices keep their
+   order, so the result feeds geohip_traj_gather and geohip_tstats unchanged; a one-point
+   trajectory is kept like any other.  Outputs (device): out_traj_of[n] (0xffffffff for a point of
+   no kept trajectory), out_traj_first and hit_traj (room for n_traj entries; hit_traj[t'] = the
+   old number of kept trajectory t'), out_traj_off (n_traj + 1), out_perm (n_sel); *n_hit_traj
+   and *n_hit_sel are host.  GEOHIP_ERR_ARG for a malformed group, as geohip_tstats: a perm
+   entry >= n, traj_off not ascending or past n_sel; also a traj_of entry >= n_traj or a perm
+   entry outside its trajectory's slice.  Device memory only; n <= 2^30. */
+int geohip_traj_filter_hit(geohip_ctx* ctx, const uint32_t* traj_of, const uint32_t* traj_first,
+                           const uint32_t* traj_off, const uint32_t* perm, uint64_t n, uint64_t n_traj, uint64_t n_sel,
+                           const uint8_t* cls, uint32_t threshold, uint32_t* out_traj_of, uint32_t* out_traj_first,
+                           uint32_t* out_traj_off, uint32_t* out_perm, uint32_t* hit_traj, uint64_t* n_hit_traj,
+                           uint64_t* n_hit_sel);
+
 /* ---- host-side planning introspection (no device needed) ------------------------------ */
 /* Query-cell sets of a point query as rectangles: point in G iff in any g rect; point in C
    iff in the c rect and not in G.  Returns GEOHIP_ERR_ARG where the reference throws. */
@@ -522,6 +575,15 @@ int geohip_plan_point(const geohip_grid* grid, double qx, double qy, double r,
                       int32_t* layers_g, int32_t* layers_c);
 /* Cell of a coordinate (HelperClass.assignGridCellID) computed by the planner. */
 int geohip_plan_cell(const geohip_grid* grid, double x, double y, int32_t* cx, int32_t* cy);
+/* Each polygon's gridIDsSet (HelperClass.assignGridCellID(bbox), HelperClass.java:123-143) as its
+   unclipped cell rectangle: rects[4 p ..] = x1, x2, y1, y2, the set = every (x, y) with x1 <= x <=
+   x2 and y1 <= y <= y2 (empty when x1 > x2 or y1 > y2).  The cell side of geohip_trange_classify.
+   Polygons as geohip_range_ppoly takes them and built the same way (ring closing, shell and
+   holes by area, the same GEOHIP_ERR_ARG cases); GEOHIP_ERR_ARG too when a non-empty range
+   leaves [-9999, 99999] or its upper index is INT_MAX.  Host memory, no device. */
+int geohip_plan_polygon_cells(const geohip_grid* grid, const uint32_t* poly_rings /* nullable */,
+                              const uint32_t* ring_off, const double* vx, const double* vy, uint64_t nv,
+                              uint32_t npoly, int32_t* rects /* 4 per polygon */);
 
 /* ---- synthetic window generators (bench / tests), device pointers --------------------- */
 /* x[i] = min_x + u(seed, 2(base+i)) * (max_x - min_x), y likewise with 2(base+i)+1, where

@@ -247,6 +247,7 @@ _SIGS = {
     "geohip_plan_point": (c_int, [POINTER(Grid), c_double, c_double, c_double, POINTER(Rect), POINTER(c_uint32),
                                   POINTER(Rect), POINTER(c_uint32), POINTER(c_int32), POINTER(c_int32)]),
     "geohip_plan_cell": (c_int, [POINTER(Grid), c_double, c_double, POINTER(c_int32), POINTER(c_int32)]),
+    "geohip_plan_polygon_cells": (c_int, [POINTER(Grid), _P, _P, _P, _P, c_uint64, c_uint32, _P]),
     "geohip_synth_uniform_async": (c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint64, c_double, c_double, c_double,
                                            c_double]),
     "geohip_ingest_points": (c_int, [_P, POINTER(Grid), POINTER(IngestSpec), _P, c_uint64, _P, _P, _P, _P, c_uint64,
@@ -266,6 +267,11 @@ _SIGS = {
     "geohip_tstats": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
     "geohip_traj_gather": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
     "geohip_traj_selected": (c_int, [_P, _P, c_uint64, _P, POINTER(c_uint64)]),
+    "geohip_trange_classify": (c_int, [_P, POINTER(Grid), _P, _P, c_uint64, _P, _P, _P, _P, c_uint64, c_uint32, _P, _P,
+                                       c_uint64, POINTER(c_uint64)]),
+    "geohip_traj_filter_hit": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_uint64, c_uint64, _P, c_uint32, _P, _P, _P, _P, _P,
+                                       POINTER(c_uint64), POINTER(c_uint64)]),
+    "geohip_debug_trange_cell_budget": (c_int, [_P, c_uint64]),
     "geohip_debug_selftest_fp64": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, _P]),
     "geohip_debug_classify": (c_int, [POINTER(Grid), c_double, c_double, c_double, _P, _P, c_uint64, _P]),
     "geohip_debug_knn_pass_stats": (c_int, [_P, _P]),
@@ -326,6 +332,19 @@ def plan_cell(grid: Grid, x: float, y: float):
     cx, cy = c_int32(0), c_int32(0)
     lib.geohip_plan_cell(ctypes.byref(grid), x, y, ctypes.byref(cx), ctypes.byref(cy))
     return cx.value, cy.value
+
+
+def plan_polygon_cells(grid: Grid, ring_off, vx, vy, poly_rings=None) -> np.ndarray:
+    """Planner introspection (host only): each polygon's unclipped bbox cell rectangle, int32
+    [npoly, 4] = (x1, x2, y1, y2) -- its gridIDsSet, the cell side of ``Context.trange_classify``.
+    Polygons as ``Context.range_ppoly`` takes them."""
+    pr, ring_off, vx, vy, npoly = _poly_arrays(poly_rings, ring_off, vx, vy)
+    rects = np.zeros((max(npoly, 1), 4), np.int32)
+    rc = lib.geohip_plan_polygon_cells(ctypes.byref(grid), _ptr(pr), _ptr(ring_off), _ptr(vx), _ptr(vy), len(vx), npoly,
+                                       _ptr(rects))
+    if rc:
+        raise _ERRORS.get(rc, GeohipError)(f"plan_polygon_cells failed ({rc})")
+    return rects[:npoly]
 
 
 def debug_ingest_record(spec: IngestSpec, rec: bytes):
@@ -1178,6 +1197,75 @@ class Context:
         rc = lib.geohip_traj_selected(self.h, traj_of.data_ptr(), n, out.data_ptr(), ctypes.byref(cnt))
         self._check(rc, "traj_selected")
         return out[:cnt.value]
+
+    # ---- trajectory range query ------------------------------------------------------------
+    def debug_trange_cell_budget(self, cells: int):
+        """Test hook: the cell budget of trange_classify's cell -> polygon table (0 = the default);
+        below the polygons' bounding cell rectangle the rectangle-scan path runs."""
+        self._check(lib.geohip_debug_trange_cell_budget(self.h, int(cells)), "debug_trange_cell_budget")
+
+    def trange_classify(self, grid: Grid, x, y, ring_off, vx, vy, poly_rings=None, want_idx=True, cap=None):
+        """geohip_trange_classify (x, y device tensors; polygons host, as for range_ppoly): per
+        point 0 = its cell is in no polygon's cell set, 1 = in the set and contained in no polygon,
+        2 = contained (strict interior) in some polygon.  Returns (cls uint8 [n], idx int32 of the
+        class-2 points ascending, or None without ``want_idx``)."""
+        import torch
+        self._dev(x, "x")
+        self._dev(y, "y")
+        n = x.numel()
+        if y.numel() != n:
+            raise GeohipArgumentError("trange_classify: x and y differ in length")
+        pr, ring_off, vx, vy, npoly = _poly_arrays(poly_rings, ring_off, vx, vy)
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        cls = torch.empty(max(n, 1), dtype=torch.uint8, device=x.device)
+        cnt = c_uint64(0)
+        call = lambda out, room: lib.geohip_trange_classify(  # noqa: E731
+            self.h, ctypes.byref(grid), x.data_ptr(), y.data_ptr(), n, _ptr(pr), _ptr(ring_off), _ptr(vx), _ptr(vy),
+            len(vx), npoly, cls.data_ptr(), out, room, ctypes.byref(cnt))
+        if not want_idx:
+            self._check(call(None, 0), "trange_classify")
+            return cls[:n], None
+        room = n if cap is None else int(cap)
+        idx = torch.empty(max(room, 1), dtype=torch.int32, device=x.device)
+        rc = call(idx.data_ptr(), room)
+        if rc == ERR_CAPACITY:
+            err = GeohipCapacityError(f"trange_classify: {lib.geohip_last_error(self.h).decode(errors='replace')}")
+            err.count = cnt.value
+            raise err
+        self._check(rc, "trange_classify")
+        return cls[:n], idx[:cnt.value]
+
+    def traj_filter_hit(self, group, cls, threshold=2):
+        """geohip_traj_filter_hit: the trajectories of a ``traj_group`` result owning a point with
+        cls >= threshold, as a group of the same shape (plus ``hit_traj``: their old numbers) for
+        ``traj_gather`` / ``tstats``."""
+        import torch
+        traj_of, first, off, perm = group["traj_of"], group["traj_first"], group["traj_off"], group["perm"]
+        self._dev(traj_of, "traj_of", "int32")
+        self._dev(off, "traj_off", "int32")
+        self._dev(cls, "cls", "uint8")
+        n, T, ns = traj_of.numel(), off.numel() - 1, perm.numel()
+        if T < 0 or first.numel() != T:
+            raise GeohipArgumentError("traj_filter_hit: traj_off needs T + 1 entries and traj_first T")
+        if cls.numel() != n:
+            raise GeohipArgumentError("traj_filter_hit: cls and traj_of differ in length")
+        if T:
+            self._dev(first, "traj_first", "int32")
+            self._dev(perm, "perm", "int32")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        mk = lambda m: torch.empty(max(m, 1), dtype=torch.int32, device=traj_of.device)  # noqa: E731
+        o_of, o_first, o_off, o_perm, hit = mk(n), mk(T), mk(T + 1), mk(ns), mk(T)
+        nt, nsel = c_uint64(0), c_uint64(0)
+        rc = lib.geohip_traj_filter_hit(self.h, traj_of.data_ptr(), first.data_ptr(), off.data_ptr(), perm.data_ptr(), n, T,
+                                        ns, cls.data_ptr(), int(threshold), o_of.data_ptr(), o_first.data_ptr(),
+                                        o_off.data_ptr(), o_perm.data_ptr(), hit.data_ptr(), ctypes.byref(nt),
+                                        ctypes.byref(nsel))
+        self._check(rc, "traj_filter_hit")
+        Th = nt.value
+        return {"traj_of": o_of[:n], "traj_first": o_first[:Th], "traj_off": o_off[:Th + 1], "perm": o_perm[:nsel.value],
+                "n_traj": Th, "n_sel": nsel.value, "hit_traj": hit[:Th]}
 
     def synth_uniform_async(self, x, y, base, seed, bbox):
         self._dev(x, "x")

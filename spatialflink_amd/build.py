@@ -35,6 +35,7 @@ SOURCES = {
     "format.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "sort.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "traj.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
+    "trange.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
 }
 
 

@@ -23,6 +23,7 @@
 #include "join.h"
 #include "pp_kernels.h"
 #include "ppoly.h"
+#include "trange.h"
 
 using namespace geohip;
 
@@ -134,6 +135,7 @@ struct geohip_ctx {
     hipEvent_t switch_ev = nullptr;  // orders a stream rebinding after the old stream's work
     void* pcache = nullptr;          // point-polygon plan cache (cell_kernels.hip owns the type)
     void* kcache = nullptr;          // point-polygon kNN polygon cache (cell_kernels.hip owns the type)
+    void* tcache = nullptr;          // trajectory range polygon plan and device tables (trange.hip owns the type)
 };
 
 namespace {
@@ -711,6 +713,7 @@ int geohip_ctx_destroy(geohip_ctx* ctx) {
     if (!ctx) return GEOHIP_ERR_ARG;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
+    trange_cache_drop(ctx);
     for (int s = 0; s < S_COUNT; s++)
         if (ctx->buf[s]) hipFree(ctx->buf[s]);
     for (auto& p : ctx->pending) {
@@ -1223,6 +1226,13 @@ int geohip_plan_cell(const geohip_grid* grid, double x, double y, int32_t* cx, i
     return cell_of(*grid, x, y, cx, cy);
 }
 
+int geohip_plan_polygon_cells(const geohip_grid* grid, const uint32_t* poly_rings, const uint32_t* ring_off,
+                              const double* vx, const double* vy, uint64_t nv, uint32_t npoly, int32_t* rects) {
+    if (!grid || (npoly && !rects)) return GEOHIP_ERR_ARG;
+    std::string err;
+    return plan_trange(*grid, poly_rings, ring_off, vx, vy, nv, npoly, 0, rects, nullptr, &err);
+}
+
 int geohip_synth_uniform_async(geohip_ctx* ctx, double* x, double* y, uint64_t n, uint64_t base, uint64_t seed,
                                double min_x, double max_x, double min_y, double max_y) {
     int rc = begin(ctx);
@@ -1406,6 +1416,7 @@ int ctx_fault_block(geohip_ctx* ctx, unsigned** out) {
 }
 void** ctx_pcache_slot(geohip_ctx* ctx) { return &ctx->pcache; }
 void** ctx_kcache_slot(geohip_ctx* ctx) { return &ctx->kcache; }
+void** ctx_tcache_slot(geohip_ctx* ctx) { return &ctx->tcache; }
 void ctx_timing_events(geohip_ctx* ctx, hipEvent_t* e0, hipEvent_t* e1) { timing_events(ctx, e0, e1); }
 void ctx_kernel_events(geohip_ctx* ctx, hipEvent_t* e0, hipEvent_t* e1) { timed_pair(ctx, e0, e1, 1); }
 void ctx_kernel_step_events(geohip_ctx* ctx, hipEvent_t* e0, hipEvent_t* e1) { timed_pair(ctx, e0, e1, 2); }

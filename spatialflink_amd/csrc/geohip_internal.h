@@ -66,4 +66,32 @@ int plan_polygon_rings(const geohip_grid& g, const uint32_t* ring_off, uint32_t 
 int build_polygon_rings(const uint32_t* ring_off, uint32_t nring, const double* vx, const double* vy,
                         PolyPlan* out, std::string* err);
 
+// Plan of a polygon set for the trajectory range query (PointPolygonTRangeQuery.java:55-59, 92-97):
+// each polygon's rings as createPolygon builds them, its unclipped bbox cell rectangle
+// (HelperClass.assignGridCellID(bbox), HelperClass.java:123-143), and the cell -> polygon lists.
+struct TRangePolygon {
+    uint32_t voff, nv;    // closed rings back to back in vx / vy, shell first
+    uint32_t nring, eoff; // ring j's envelope at env[4 * (eoff + j) ...] (minx, miny, maxx, maxy)
+    double bb[4];         // the shell's envelope (JTS Polygon envelope)
+    int32_t rect[4];      // x1, x2, y1, y2 of gridIDsSet; x1 > x2 or y1 > y2: the set is empty
+};
+// Cell budget of the cell -> polygon CSR: it is built when the bounding rectangle of every
+// polygon rectangle holds at most this many cells (16 MiB of offsets) and the lists at most four
+// times as many entries; beyond that the device scans the rectangle list per point.
+constexpr uint64_t kTRangeCellBudget = 1ull << 22;
+struct TRangePlan {
+    std::vector<TRangePolygon> polys;
+    std::vector<double> vx, vy, env;
+    std::vector<uint16_t> vr;         // ring id per vertex (within its polygon)
+    int32_t bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;  // bounding rectangle of the non-empty rectangles
+    bool csr = false;
+    // csr: cell (cx, cy) of the bounding rectangle = entry (cx - bx0) * (by1 - by0 + 1) + (cy - by0);
+    // its polygons, ascending, are cell_poly[cell_off[k] .. cell_off[k + 1])
+    std::vector<uint32_t> cell_off, cell_poly;
+};
+// plan may be null (rectangles only); rects (nullable) receives 4 per polygon.
+int plan_trange(const geohip_grid& g, const uint32_t* poly_rings, const uint32_t* ring_off, const double* vx,
+                const double* vy, uint64_t nv, uint32_t npoly, uint64_t cell_budget, int32_t* rects,
+                TRangePlan* plan, std::string* err);
+
 }  // namespace geohip

@@ -444,4 +444,98 @@ int plan_polygon_rings(const geohip_grid& g, const uint32_t* ring_off, uint32_t 
     return GEOHIP_OK;
 }
 
+// PointPolygonTRangeQuery's polygon side (tRange/PointPolygonTRangeQuery.java:55-59, 92-97):
+// polygonsGridCellIDs = the union of each polygon's gridIDsSet = assignGridCellID(bbox)
+// (HelperClass.java:123-143), every (x, y) of the bbox corners' cell range, not clipped to the
+// grid.  The reference compares "%05d%05d" strings; with every polygon index in [-9999, 99999]
+// each polygon key has 5 + 5 characters, so a point key equals one iff the integer pairs are
+// equal -- outside that range the strings can collide, which this plan does not model:
+// GEOHIP_ERR_ARG.  Likewise where the bbox loop never ends (upper index INT_MAX).
+int plan_trange(const geohip_grid& g, const uint32_t* poly_rings, const uint32_t* ring_off, const double* vx,
+                const double* vy, uint64_t nv, uint32_t npoly, uint64_t cell_budget, int32_t* rects,
+                TRangePlan* plan, std::string* err) {
+    int rc = check_grid(g, err);
+    if (rc) return rc;
+    if (npoly && (!ring_off || !vx || !vy)) { *err = "null polygon arrays"; return GEOHIP_ERR_ARG; }
+    auto ring_of = [&](uint32_t p) { return poly_rings ? poly_rings[p] : p; };
+    for (uint32_t p = 0; p < npoly; p++)
+        if (ring_of(p + 1) <= ring_of(p)) { *err = "poly_rings not strictly ascending (a polygon needs a ring)"; return GEOHIP_ERR_ARG; }
+    if (npoly) {
+        const uint32_t R0 = ring_of(0), R1 = ring_of(npoly);
+        for (uint32_t j = R0; j < R1; j++)
+            if (ring_off[j + 1] < ring_off[j]) { *err = "ring_off not ascending"; return GEOHIP_ERR_ARG; }
+        if (ring_off[R1] > nv) { *err = "ring_off refers past the nv vertices of vx / vy"; return GEOHIP_ERR_ARG; }
+    }
+    TRangePlan local;
+    TRangePlan& out = plan ? *plan : local;
+    out = TRangePlan();
+    out.polys.resize(npoly);
+    int64_t bx0 = INT32_MAX, bx1 = INT32_MIN, by0 = INT32_MAX, by1 = INT32_MIN;
+    uint64_t entries = 0;
+    for (uint32_t p = 0; p < npoly; p++) {
+        PolyPlan pl;
+        const uint32_t r0 = ring_of(p), nring = ring_of(p + 1) - r0;
+        if (nring > 65535) { *err = "polygon with more than 65535 rings"; return GEOHIP_ERR_UNSUPPORTED; }
+        rc = build_polygon_rings(ring_off + r0, nring, vx, vy, &pl, err);
+        if (rc) return rc;
+        TRangePolygon& P = out.polys[p];
+        P.voff = (uint32_t)out.vx.size();
+        P.nv = (uint32_t)pl.rx.size();
+        P.nring = (uint32_t)pl.ring_start.size() - 1;
+        P.eoff = (uint32_t)(out.env.size() / 4);
+        out.vx.insert(out.vx.end(), pl.rx.begin(), pl.rx.end());
+        out.vy.insert(out.vy.end(), pl.ry.begin(), pl.ry.end());
+        // ring envelopes as JTS computes them (Envelope.expandToInclude: NaN never enters)
+        for (uint32_t j = 0; j < P.nring; j++) {
+            const uint32_t a = pl.ring_start[j], b = pl.ring_start[j + 1];
+            double mnx = pl.rx[a], mxx = pl.rx[a], mny = pl.ry[a], mxy = pl.ry[a];
+            for (uint32_t i = a; i < b; i++) {
+                out.vr.push_back((uint16_t)j);
+                const double x = pl.rx[i], y = pl.ry[i];
+                if (x < mnx) mnx = x;
+                if (x > mxx) mxx = x;
+                if (y < mny) mny = y;
+                if (y > mxy) mxy = y;
+            }
+            out.env.insert(out.env.end(), {mnx, mny, mxx, mxy});
+            if (j == 0) { P.bb[0] = mnx; P.bb[1] = mny; P.bb[2] = mxx; P.bb[3] = mxy; }
+        }
+        int32_t x1, y1, x2, y2;
+        cell_of(g, P.bb[0], P.bb[1], &x1, &y1);
+        cell_of(g, P.bb[2], P.bb[3], &x2, &y2);
+        P.rect[0] = x1; P.rect[1] = x2; P.rect[2] = y1; P.rect[3] = y2;
+        if (rects) memcpy(rects + 4 * (size_t)p, P.rect, sizeof P.rect);
+        if (x1 > x2 || y1 > y2) continue;  // gridIDsSet empty
+        if (x2 == INT32_MAX || y2 == INT32_MAX) { *err = "reference bbox loop does not terminate"; return GEOHIP_ERR_ARG; }
+        if (x1 < -9999 || x2 > 99999 || y1 < -9999 || y2 > 99999) {
+            *err = "polygon bbox cells leave [-9999, 99999]: the reference's string keys stop being unique";
+            return GEOHIP_ERR_ARG;
+        }
+        bx0 = std::min<int64_t>(bx0, x1); bx1 = std::max<int64_t>(bx1, x2);
+        by0 = std::min<int64_t>(by0, y1); by1 = std::max<int64_t>(by1, y2);
+        entries += (uint64_t)(x2 - x1 + 1) * (uint64_t)(y2 - y1 + 1);
+    }
+    if (bx0 > bx1) return GEOHIP_OK;  // no polygon covers a cell
+    out.bx0 = (int32_t)bx0; out.bx1 = (int32_t)bx1; out.by0 = (int32_t)by0; out.by1 = (int32_t)by1;
+    if (!plan) return GEOHIP_OK;
+    const uint64_t W = (uint64_t)(bx1 - bx0 + 1), H = (uint64_t)(by1 - by0 + 1);
+    if (W * H > cell_budget || entries > 4 * cell_budget || entries >= 0xffffffffull) return GEOHIP_OK;
+    out.cell_off.assign(W * H + 1, 0u);
+    auto each_cell = [&](auto&& f) {
+        for (uint32_t p = 0; p < npoly; p++) {
+            const int32_t* R = out.polys[p].rect;
+            if (R[0] > R[1] || R[2] > R[3]) continue;
+            for (int64_t a = R[0]; a <= R[1]; a++)
+                for (int64_t b = R[2]; b <= R[3]; b++) f((uint64_t)(a - bx0) * H + (uint64_t)(b - by0), p);
+        }
+    };
+    each_cell([&](uint64_t k, uint32_t) { out.cell_off[k + 1]++; });
+    for (uint64_t k = 0; k < W * H; k++) out.cell_off[k + 1] += out.cell_off[k];
+    out.cell_poly.assign(entries, 0u);
+    std::vector<uint32_t> cur(out.cell_off.begin(), out.cell_off.end() - 1);
+    each_cell([&](uint64_t k, uint32_t p) { out.cell_poly[cur[k]++] = p; });  // polygons ascending per cell
+    out.csr = true;
+    return GEOHIP_OK;
+}
+
 }  // namespace geohip

@@ -15,6 +15,7 @@ MI355X through libgeohip:
 ``PointPolygonRangeQuery.run``        ``spatialOperators/range/PointPolygonRangeQuery.java:30-128``
 ``PointTStatsQuery.run`` (window)     ``spatialOperators/tStats/PointTStatsQuery.java:64-92``, ``TStatsQuery.java:148-189``
 ``PointTFilterQuery.run``             ``spatialOperators/tFilter/PointTFilterQuery.java:30-118``
+``PointPolygonTRangeQuery.run``       ``spatialOperators/tRange/PointPolygonTRangeQuery.java:53-177``
 ====================================  =========================================================
 
 Window contents are columnar (``PointWindow``: x, y and optional object ids); results are
@@ -337,6 +338,42 @@ class PointTFilterQuery(_TrajOperator):
         off = g["traj_off"].cpu().tolist()
         ids = self._obj_ids(window, g["traj_first"])
         return [(ids[t], xy[off[t]:off[t + 1]]) for t in range(g["n_traj"])]
+
+
+class PointPolygonTRangeQuery(_TrajOperator):
+    """PointPolygonTRangeQuery.run (tRange/PointPolygonTRangeQuery.java:53-177) against a set of
+    polygons built on the operator's grid.  A point counts when its cell is in some polygon's
+    gridIDsSet and some polygon contains it (JTS ``contains``: strict interior, the boundary is
+    outside).  RealTime (:53-87): those points' window indices, ascending; a null objID on a point
+    whose cell is in the set is Flink's null-key error, elsewhere it is dropped by the filter.
+    WindowBased (:90-177): per trajectory with such a point (objID, coords [k, 2]) of all its
+    points in the window, in arrival order, trajectories in order of first appearance; every
+    point is keyed there, so any null objID is an error."""
+
+    def run(self, window: TrajectoryWindow, polygon_set):
+        self._check_type()
+        if self.index is None:
+            raise _abi.GeohipArgumentError("PointPolygonTRangeQuery needs the grid that assigned the cells")
+        polys = [polygon_set] if isinstance(polygon_set, Polygon) else list(polygon_set)
+        pr, off, vx, vy = _rings(polys)
+        ctx = self._ctx()
+        if self.conf.query_type == QueryType.RealTime:
+            cls, idx = ctx.trange_classify(self.index.abi(), window.x, window.y, off, vx, vy, poly_rings=pr)
+            n = len(window)
+            if n and bool(((window.oid_off[:n] < 0) & (cls >= 1)).any()):
+                raise _abi.GeohipArgumentError("a null objID on a point inside the polygons' cells "
+                                               "(keyBy of a null key throws)")
+            return idx
+        g = self._group(window, ())
+        if not polys:
+            return []
+        cls, _ = ctx.trange_classify(self.index.abi(), window.x, window.y, off, vx, vy, poly_rings=pr, want_idx=False)
+        h = ctx.traj_filter_hit(g, cls, threshold=2)
+        gx, gy = ctx.traj_gather(window.x, window.y, h["perm"])
+        xy = np.stack([gx.cpu().numpy(), gy.cpu().numpy()], axis=1) if h["n_sel"] else np.zeros((0, 2))
+        o = h["traj_off"].cpu().tolist()
+        ids = self._obj_ids(window, h["traj_first"])
+        return [(ids[t], xy[o[t]:o[t + 1]]) for t in range(h["n_traj"])]
 
 
 def _rings(polys):
