@@ -1004,7 +1004,8 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
                 unsigned long long ed = kSentinelD;
                 unsigned ei = kSentinelI;
                 if (t < nl) {
-                    if (t % io.list_cap < (io.len[t / io.list_cap] & ~kLenWhole)) {
+                    // (a slot-complete block's length word carries kLenSlots: its list holds its slots)
+                    if (t % io.list_cap < (io.len[t / io.list_cap] & ~(kLenWhole | kLenSlots))) {
                         ed = io.list_d[t];
                         ei = io.list_i[t];
                     }

@@ -104,6 +104,35 @@ def pair_digest(pairs, chunk=1 << 26):
     return m, h
 
 
+# ---- join binning geometry (tests/test_gpu_join_mid.py, tests/test_gpu_arrival.py)
+def binning_shape(x, y, nb=500):
+    """(largest tile, tiles over one round, largest non-empty segment count of a band, largest
+    count of one tile within one segment) of the join binning for this window (join_bin: <= 256
+    level-1 blocks of >= 16384 points, 4096-point sub-chunks = segments, tiles of ceil(nb / 128)
+    cells, 128 tiles per band; jb_tiles takes a segment's records of a tile kJbRound = 1024 at a
+    time)."""
+    n = len(x)
+    l = (BJ[1] - BJ[0]) / nb
+    ts = (nb + 127) // 128
+    nt = (nb + ts - 1) // ts
+    with np.errstate(invalid="ignore"):
+        fx, fy = np.floor((x - BJ[0]) / l), np.floor((y - BJ[2]) / l)
+    ok = (fx >= 0) & (fx < nb) & (fy >= 0) & (fy < nb)  # NaN: not ok
+    cx = np.where(ok, fx, 0).astype(np.int64)
+    cy = np.where(ok, fy, 0).astype(np.int64)
+    tile = (cx // ts) * nt + cy // ts
+    cnt = np.bincount(tile[ok], minlength=nt * nt)
+    nblk = min(256, max(1, (n + 16383) // 16384))
+    chunk = (n + nblk - 1) // nblk
+    nsub = (chunk + 4095) // 4096
+    i = np.arange(n)
+    seg = (i // chunk) * nsub + (i % chunk) // 4096
+    key = (tile[ok] >> 7) * (nblk * nsub) + seg[ok]
+    band_of = np.unique(key) // (nblk * nsub)
+    per_seg = np.unique(tile[ok] * (nblk * nsub) + seg[ok], return_counts=True)[1]
+    return int(cnt.max()), int((cnt > 2048).sum()), int(np.bincount(band_of).max()), int(per_seg.max())
+
+
 # ---- point-polygon windows around the grid edge (tests/test_gpu_ppoly_tiles.py)
 def edge_window(n, seed, off, vx, vy):
     """Uniform points, every vertex and edge midpoint, points around the grid's west edge (in

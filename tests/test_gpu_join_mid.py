@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 import cref
-from helpers import pair_digest
+from helpers import binning_shape, pair_digest
 from spatialflink_amd import _abi, synth
 
 pytestmark = pytest.mark.gpu
@@ -36,29 +36,6 @@ SHAPES = [(4_000_000, 0.03, 2000, 0.03, 0.05), (4_000_000, 0.01, 1000, 0.02, 0.0
 def agrid(n):
     l = (BJ[1] - BJ[0]) / n
     return _abi.make_grid(BJ[0], BJ[2], l, n), cref.grid(BJ[0], BJ[2], l, n)
-
-
-def binning_shape(x, y, nb=500):
-    """(largest tile, tiles over one round, largest non-empty segment count of a band) of the
-    join binning for this window (join_bin: <= 256 level-1 blocks of >= 16384 points, 4096-point
-    sub-chunks, tiles of ceil(nb / 128) cells, 128 tiles per band)."""
-    n = len(x)
-    l = (BJ[1] - BJ[0]) / nb
-    ts = (nb + 127) // 128
-    nt = (nb + ts - 1) // ts
-    cx = np.floor((x - BJ[0]) / l).astype(np.int64)
-    cy = np.floor((y - BJ[2]) / l).astype(np.int64)
-    ok = (cx >= 0) & (cx < nb) & (cy >= 0) & (cy < nb)
-    tile = (cx // ts) * nt + cy // ts
-    cnt = np.bincount(tile[ok], minlength=nt * nt)
-    nblk = min(256, max(1, (n + 16383) // 16384))
-    chunk = (n + nblk - 1) // nblk
-    nsub = (chunk + 4095) // 4096
-    i = np.arange(n)
-    seg = (i // chunk) * nsub + (i % chunk) // 4096
-    key = (tile[ok] >> 7) * (nblk * nsub) + seg[ok]
-    band_of = np.unique(key) // (nblk * nsub)
-    return int(cnt.max()), int((cnt > 2048).sum()), int(np.bincount(band_of).max())
 
 
 def full_all_chunks(x, y, qx, qy, r, nb=500):
@@ -89,7 +66,7 @@ def mid_window(request):
     n, sig, nq, qsig, r = SHAPES[request.param]
     hx, hy = synth.gaussian_clusters(n, 11 + request.param, sigma=sig)
     hqx, hqy = synth.gaussian_clusters(nq, 21 + request.param, sigma=qsig)
-    big, over, segs = binning_shape(hx, hy)
+    big, over, segs, _ = binning_shape(hx, hy)
     assert over > 0 and big > 2 * 2048, (big, over)   # tiles spanning several level-2 rounds
     assert segs > 512, segs                          # bands read in several segment windows
     assert full_all_chunks(hx, hy, hqx[:200], hqy[:200], r) > 0  # full-chunk ALL runs

@@ -461,14 +461,20 @@ def test_knn_equal_distance_shell(ctx):
 
 
 def test_knn_query_duplicates_spill_and_repeat(ctx):
-    """Thousands of exact copies of the query point in consecutive window slots: one scan
-    block keeps far more than its LDS survivor buffer (spill path), the heads' k-th bin is the
-    lowest and lists are read whole.  Every call is repeated on the same context: the arrival
-    tickets and the spill count must be back at zero after each launch."""
+    """Thousands of exact copies of the query point in consecutive window slots, and 3500 more on
+    the slots of one scan block: that block keeps more than its LDS survivor buffer (spill path,
+    asserted through the pass's counters), the heads' k-th bin is the lowest and lists are read
+    whole.  Every call is repeated on the same context: the arrival tickets and the spill count
+    must be back at zero after each launch.
+
+    The consecutive copies alone do not spill: the pass interleaves its 256-point iterations
+    across the blocks, so 5000 consecutive copies spread over about 20 blocks, 250 each, against
+    kCap = 3072 (the counters read spilled = 0 for them)."""
     _dup_spill_repeat(ctx)
 
 
 def _dup_spill_repeat(ctx):
+    import arrivals
     ag, cg = agrid(100)
     rng = np.random.default_rng(17)
     x, y = _window(rng, 2_000_000)
@@ -477,11 +483,18 @@ def _dup_spill_repeat(ctx):
     sc = rng.integers(0, 2_000_000, 300)
     x[sc] = Q[0]
     y[sc] = Q[1]
+    # one block of the host window's last staged pass (its counters are the ones read back)
+    blk = arrivals.knn_block_of(len(x), host=True)
+    slots = np.flatnonzero(blk == blk.max() - 7)
+    assert len(slots) >= 3500 > arrivals.PASS_CAP
+    x[slots[:3500]] = Q[0]
+    y[slots[:3500]] = Q[1]
     for k in (1, 50, 256):
         wi, wd = cref.knn_pp(cg, x, y, Q[0], Q[1], 0.5, k)
         for _ in range(2):
             oi, od = ctx.knn_pp(ag, x, y, Q[0], Q[1], 0.5, k)
             assert oi.tolist() == wi.tolist() and np.array_equal(od.view(np.uint64), wd.view(np.uint64))
+            assert ctx.debug_knn_pass_stats()[1] > 0  # a copy of q survives any bound: 3500 > kCap of them spill
     # then a plain window again: no state left behind by the spill
     x2, y2 = _window(rng, 1_000_000)
     wi, wd = cref.knn_pp(cg, x2, y2, Q[0], Q[1], 0.5, 50)
