@@ -27,6 +27,8 @@
  *   geohip_trange_classify <- PointPolygonTRangeQuery's cell filter and contains test
  *                         spatialOperators/tRange/PointPolygonTRangeQuery.java:55-81, 92-130
  *   geohip_traj_filter_hit <- its window join back to the whole trajectories   :140-177
+ *   geohip_tagg_cells  <- PointTAggregateQuery's window function    spatialOperators/tAggregate/PointTAggregateQuery.java:63-99,
+ *                                                                      tAggregate/TAggregateQuery.java:397-493, 514-613
  *   geohip_grid        <- UniformGrid getters                      spatialIndices/UniformGrid.java:136-146
  *                         (values copied from the Java object, so both constructors :47-85 are covered)
  *
@@ -491,6 +493,18 @@ int geohip_traj_group(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* 
                       const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint32_t* traj_of,
                       uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm, uint64_t cap_traj,
                       uint64_t* n_traj, uint64_t* n_sel);
+/* geohip_traj_group with flags (0: exactly that call).
+     GEOHIP_TRAJ_NULL_KEY  with s == 0 a null objID is not an error: the null points form one
+       trajectory, numbered by first appearance like any other, whose traj_first entry names a
+       point with bit 63 of oid_off set; it never equals "".  For operators that key by something
+       else and keep the objIDs in a HashMap, which admits the null key (TAggregateQuery.java:
+       528-572).  With s > 0 a null objID is still in no set.
+   GEOHIP_ERR_ARG for an unknown flag. */
+#define GEOHIP_TRAJ_NULL_KEY 1u
+int geohip_traj_group_flags(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oid_off, uint64_t n,
+                            const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint32_t* traj_of,
+                            uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm, uint64_t cap_traj,
+                            uint64_t* n_traj, uint64_t* n_sel, uint32_t flags);
 /* Windowed PointTStatsQuery: TStatsQueryWFunction.apply (tStats/TStatsQuery.java:148-189) per
    trajectory of a geohip_traj_group result over the window's x / y / ts (n entries each):
      last = 0, S = 0.0, T = 0; for each point in arrival order:
@@ -566,6 +580,56 @@ int geohip_traj_filter_hit(geohip_ctx* ctx, const uint32_t* traj_of, const uint3
                            const uint8_t* cls, uint32_t threshold, uint32_t* out_traj_of, uint32_t* out_traj_first,
                            uint32_t* out_traj_off, uint32_t* out_perm, uint32_t* hit_traj, uint64_t* n_hit_traj,
                            uint64_t* n_hit_sel);
+
+/* ---- per-cell trajectory aggregate (PointTAggregateQuery, window form) ------------------- */
+/* The heat-map query: per grid cell how many objIDs were in it and how long each stayed
+   (spatialOperators/tAggregate/PointTAggregateQuery.java:63-99: keyBy(p.gridID), then
+   TAggregateQuery.java:514-613 for a time window and :397-493, the same loop, for a count
+   window).  The real-time form (:53-377) reads the wall clock and is not evaluated.
+   Per cell, over its points in arrival order (ascending index), with min / max / len per objID
+   and minLen = Long.MAX_VALUE, maxLen = Long.MIN_VALUE, sum = 0:
+     first point of an objID: min = max = ts, len = 0 (touches neither sum nor the extremes);
+     later point: min = ts if ts < min; max = ts if ts > max; L = max - min (a Java long: wraps);
+                  if len != L: sum += L - len, len = L;
+                  if L > maxLen: maxLen = L, its point is remembered; if L < minLen likewise
+                  (strict: the first point in arrival order to reach a value keeps it).
+   Inputs: the window's x / y / ts (n entries) and a group over it -- traj_of[n], perm[n_sel],
+   n_traj of geohip_traj_group, geohip_traj_group_flags (GEOHIP_TRAJ_NULL_KEY: the reference's
+   maps admit the null objID) or geohip_traj_filter_hit; perm ordered by (trajectory, index) as
+   they leave it.  That order is a precondition and is NOT checked (only bounds are): a perm in
+   another order stays in bounds and returns GEOHIP_OK, but splits an objID's stay in a cell into
+   several visits and so gives wrong cells.  Points outside the group (traj_of == 0xffffffff) take
+   no part.
+   Outputs (device; every per-cell array has room for n_sel entries, cell_xy for 2 n_sel,
+   visit_off for n_sel + 1, so no capacity error exists), cells c < *n_cells in ascending
+   (cx, cy) order:
+     cell_xy[2c], cell_xy[2c+1]  the cell's unclipped indices (HelperClass.java:104-120; a NaN
+                                 coordinate is index 0); the reference's key is their "%05d%05d";
+     cell_count[c]               distinct objIDs (trackerIDTrajLength.size());
+     cell_sum[c]                 sum (SUM emits it when > 0, :581);
+     cell_avg[c]                 Math.round(sum * 1.0 / (count * 1.0)) (:589; JDK 8: floor(a + 1/2)
+                                 on the bits, (long) a beyond 2^52), 0 where sum <= 0;
+     cell_min[c], cell_min_pt[c] minLen and the window index of the point that set it (its objID
+                                 is the reported one, :563-566); Long.MAX_VALUE and 0xffffffff
+                                 where the reference emits nothing (:596);
+     cell_max[c], cell_max_pt[c] likewise (:557-560, :603) with Long.MIN_VALUE;
+     visit_off[*n_cells + 1], visit_traj[V], visit_len[V]: the ALL map (:576-579) -- cell c's
+                                 (trajectory, final len) pairs are visits visit_off[c] ..
+                                 visit_off[c + 1], by ascending trajectory number (the
+                                 reference's order is a HashMap's).  The three may be NULL together.
+   *n_cells, *n_visits and *n_odd are host.  Cell keys are compared as integer pairs; the
+   reference's strings are the same while every index lies in [-9999, 99999] (beyond it distinct
+   cells share a key: (10000, 100001) and (100001, 1)), so a selected point whose index on either
+   axis leaves that range -- the saturated indices of +-infinity and huge coordinates included --
+   is GEOHIP_ERR_ARG with *n_odd = the number of such points (nothing else is promised about the
+   outputs then).  GEOHIP_ERR_ARG too for a perm entry >= n or a traj_of[perm[j]] >= n_traj (no
+   such point is read).  n_sel == 0: zero cells.  Device memory only; n <= 2^30. */
+int geohip_tagg_cells(geohip_ctx* ctx, const geohip_grid* grid, const double* x, const double* y, const int64_t* ts,
+                      uint64_t n, const uint32_t* traj_of, const uint32_t* perm, uint64_t n_sel, uint64_t n_traj,
+                      int32_t* cell_xy, uint32_t* cell_count, int64_t* cell_sum, int64_t* cell_avg, int64_t* cell_min,
+                      uint32_t* cell_min_pt, int64_t* cell_max, uint32_t* cell_max_pt, uint32_t* visit_off /* nullable */,
+                      uint32_t* visit_traj /* nullable */, int64_t* visit_len /* nullable */, uint64_t* n_cells,
+                      uint64_t* n_visits, uint64_t* n_odd);
 
 /* ---- host-side planning introspection (no device needed) ------------------------------ */
 /* Query-cell sets of a point query as rectangles: point in G iff in any g rect; point in C

@@ -142,6 +142,7 @@ def make_csv_out_spec(attrs=(0, 1, 2, 3), delimiter: str = ",") -> CsvOutSpec:
 
 
 DATE_NONE, DATE_YMD_HMS = 0, 1
+TRAJ_NULL_KEY = 1  # GEOHIP_TRAJ_NULL_KEY
 
 
 class TextOutSpec(ctypes.Structure):
@@ -262,6 +263,8 @@ _SIGS = {
     "geohip_ingest_oid_compact": (c_int, [_P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, POINTER(c_uint64)]),
     "geohip_traj_group": (c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64, POINTER(c_uint64),
                                   POINTER(c_uint64)]),
+    "geohip_traj_group_flags": (c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64, POINTER(c_uint64),
+                                        POINTER(c_uint64), c_uint32]),
     "geohip_debug_traj_group_masked": (c_int, [_P, c_uint64, _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, _P, _P, c_uint64,
                                                POINTER(c_uint64), POINTER(c_uint64)]),
     "geohip_tstats": (c_int, [_P, _P, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, _P, _P]),
@@ -271,6 +274,8 @@ _SIGS = {
                                        c_uint64, POINTER(c_uint64)]),
     "geohip_traj_filter_hit": (c_int, [_P, _P, _P, _P, _P, c_uint64, c_uint64, c_uint64, _P, c_uint32, _P, _P, _P, _P, _P,
                                        POINTER(c_uint64), POINTER(c_uint64)]),
+    "geohip_tagg_cells": (c_int, [_P, POINTER(Grid), _P, _P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, _P, _P, _P, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "geohip_debug_trange_cell_budget": (c_int, [_P, c_uint64]),
     "geohip_debug_selftest_fp64": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, _P]),
     "geohip_debug_classify": (c_int, [POINTER(Grid), c_double, c_double, c_double, _P, _P, c_uint64, _P]),
@@ -1093,13 +1098,15 @@ class Context:
         return out[:ln.value], off
 
     # ---- trajectory queries keyed by objID ------------------------------------------------
-    def traj_group(self, oid_text, oid_off, set_text=None, set_off=None, cap_traj=None, hash_mask=None):
+    def traj_group(self, oid_text, oid_off, set_text=None, set_off=None, cap_traj=None, hash_mask=None, null_key=False):
         """geohip_traj_group (device tensors: oid_text uint8, oid_off int64 [n + 1] with bit 63 = null,
         as ingest_oid_compact returns them; the trajIDSet as (set_text, set_off) in the same layout, None
         = empty): keyBy(objID) over the selected points.  Returns dict(traj_of int32 [n] (-1 = not
         selected), traj_first int32 [T], traj_off int32 [T + 1], perm int32 [n_sel], n_traj, n_sel);
         trajectory t = the t-th distinct selected objID by first appearance.  ``hash_mask``: the
-        geohip_debug_traj_group_masked test hook."""
+        geohip_debug_traj_group_masked test hook.  ``null_key``: geohip_traj_group_flags with
+        GEOHIP_TRAJ_NULL_KEY -- under an empty set the null objIDs form one trajectory and raise
+        nothing."""
         import torch
         self._dev(oid_off, "oid_off", "int64")
         n = oid_off.numel() - 1
@@ -1124,7 +1131,11 @@ class Context:
         args = (oid_text.data_ptr(), oid_off.data_ptr(), n, set_text.data_ptr() if s else None,
                 set_off.data_ptr() if s else None, s, traj_of.data_ptr(), first.data_ptr(), off.data_ptr(),
                 perm.data_ptr(), cap, ctypes.byref(nt), ctypes.byref(ns))
-        if hash_mask is None:
+        if null_key and hash_mask is not None:
+            raise GeohipArgumentError("traj_group: hash_mask (the test hook) takes no flags")
+        if null_key:
+            rc = lib.geohip_traj_group_flags(self.h, *args, TRAJ_NULL_KEY)
+        elif hash_mask is None:
             rc = lib.geohip_traj_group(self.h, *args)
         else:
             rc = lib.geohip_debug_traj_group_masked(self.h, int(hash_mask), *args)
@@ -1266,6 +1277,51 @@ class Context:
         Th = nt.value
         return {"traj_of": o_of[:n], "traj_first": o_first[:Th], "traj_off": o_off[:Th + 1], "perm": o_perm[:nsel.value],
                 "n_traj": Th, "n_sel": nsel.value, "hit_traj": hit[:Th]}
+
+    # ---- per-cell trajectory aggregate ------------------------------------------------------
+    def tagg_cells(self, grid: Grid, x, y, ts, group, visits=True):
+        """geohip_tagg_cells (x, y float64, ts int64 device tensors; ``group``: a ``traj_group`` /
+        ``traj_filter_hit`` result over the same window): the windowed PointTAggregateQuery per
+        grid cell, cells in ascending (cx, cy) order.  Returns dict(cell_xy int32 [C, 2], count
+        int32 [C], sum / avg / min / max int64 [C], min_pt / max_pt int32 [C] (-1 = nothing to
+        emit), n_cells, n_visits) and, with ``visits``, visit_off int32 [C + 1], visit_traj int32
+        [V], visit_len int64 [V]: the ALL map per cell by ascending trajectory number.  A cell
+        index outside [-9999, 99999] raises GeohipArgumentError with ``n_odd`` = such points."""
+        import torch
+        self._dev(x, "x")
+        self._dev(y, "y")
+        self._dev(ts, "ts", "int64")
+        traj_of, perm = group["traj_of"], group["perm"]
+        self._dev(traj_of, "traj_of", "int32")
+        n, ns, T = x.numel(), perm.numel(), int(group["n_traj"])
+        if ns:
+            self._dev(perm, "perm", "int32")
+        if y.numel() != n or ts.numel() != n or traj_of.numel() != n:
+            raise GeohipArgumentError("tagg_cells: x, y, ts and traj_of differ in length")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        mk = lambda m, dt: torch.empty(max(m, 1), dtype=dt, device=x.device)  # noqa: E731
+        i32, i64 = torch.int32, torch.int64
+        xy, cnt, sm, av = mk(2 * ns, i32), mk(ns, i32), mk(ns, i64), mk(ns, i64)
+        mn, mnp, mx, mxp = mk(ns, i64), mk(ns, i32), mk(ns, i64), mk(ns, i32)
+        voff, vtr, vlen = (mk(ns + 1, i32), mk(ns, i32), mk(ns, i64)) if visits else (None, None, None)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        nc, nv, odd = c_uint64(0), c_uint64(0), c_uint64(0)
+        rc = lib.geohip_tagg_cells(self.h, ctypes.byref(grid), x.data_ptr(), y.data_ptr(), ts.data_ptr(), n, traj_of.data_ptr(),
+                                   perm.data_ptr() if ns else None, ns, T, xy.data_ptr(), cnt.data_ptr(), sm.data_ptr(),
+                                   av.data_ptr(), mn.data_ptr(), mnp.data_ptr(), mx.data_ptr(), mxp.data_ptr(), ptr(voff),
+                                   ptr(vtr), ptr(vlen), ctypes.byref(nc), ctypes.byref(nv), ctypes.byref(odd))
+        if rc == ERR_ARG and odd.value:
+            err = GeohipArgumentError(f"tagg_cells: {lib.geohip_last_error(self.h).decode(errors='replace')}")
+            err.n_odd = odd.value
+            raise err
+        self._check(rc, "tagg_cells")
+        C, V = nc.value, nv.value
+        out = {"cell_xy": xy[:2 * C].view(-1, 2), "count": cnt[:C], "sum": sm[:C], "avg": av[:C], "min": mn[:C],
+               "min_pt": mnp[:C], "max": mx[:C], "max_pt": mxp[:C], "n_cells": C, "n_visits": V}
+        if visits:
+            out.update(visit_off=voff[:C + 1], visit_traj=vtr[:V], visit_len=vlen[:V])
+        return out
 
     def synth_uniform_async(self, x, y, base, seed, bbox):
         self._dev(x, "x")

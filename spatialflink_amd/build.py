@@ -36,6 +36,7 @@ SOURCES = {
     "sort.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "traj.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "trange.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
+    "tagg.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
 }
 
 

@@ -23,6 +23,8 @@
 //                      the representative's -- a hash only picks the first slot -- and a match lowers
 //                      the slot to the smaller index (atomicMin), which stays a representative, so when
 //                      the kernel ends the slot holds the string's first appearance;
+//      (GEOHIP_TRAJ_NULL_KEY: a null objID takes no slot; the null points lower one word to
+//      their smallest index, which is their representative);
 //   3. traj_flag + exclusive scan (rocPRIM): dense ids in first-appearance order;
 //   4. traj_finalize   traj_of, traj_first and the sort keys (unselected points get key T);
 //   5. stable LSD radix sort (rocPRIM) of (traj_of, index) over ceil(log2(T + 1)) bits: perm;
@@ -56,7 +58,9 @@ constexpr uint64_t kMaxPoints = 1ull << 30;  // table slots (<= 2^31) and indice
 // traj scratch slots (ctx_ensure; every call owns them for its own duration on the ctx stream)
 enum TSlot { T_TAB, T_KEY, T_RANK, T_KEY2, T_VAL, T_VAL2, T_TEMP, T_WORDS, T_SETTAB, T_LIST };
 
-// words block: [0] error bits, [1] selected points, [2] queued long trajectories
+// words block: [0] error bits, [1] selected points, [2] queued long trajectories, [3] the null
+// objID's representative (GEOHIP_TRAJ_NULL_KEY: the smallest index of a null point, kNone = none)
+constexpr unsigned kNullSlot = 0xfffffffeu;  // traj_of between traj_insert and traj_finalize: the null trajectory (no table slot)
 constexpr unsigned kErrNullKey = 1u;   // null objID under an empty set (Flink: null key)
 constexpr unsigned kErrOffsets = 2u;   // oid_off / set_off not ascending
 constexpr unsigned kErrInternal = 4u;  // a probe walked the whole table
@@ -136,15 +140,19 @@ __global__ void __launch_bounds__(kTB) traj_set_build(Strs set, unsigned s, unsi
 // traj_of[i] = the table slot of point i's objID, kNone for an unselected point.
 __global__ void __launch_bounds__(kTB) traj_insert(Strs oid, unsigned n, Strs set, unsigned s, const unsigned* set_tab,
                                                    unsigned set_mask, unsigned* tab, unsigned slots_mask, uint64_t hmask,
-                                                   unsigned* traj_of, unsigned* words) {
+                                                   unsigned null_key, unsigned* traj_of, unsigned* words) {
     const unsigned i = blockIdx.x * kTB + threadIdx.x;
     unsigned slot = kNone;
     if (i < n) {
         const unsigned long long o0 = oid.off[i], o1 = oid.off[i + 1];
         if (o0 >> 63) {
             // PointTStatsQuery.java:76-84: null is in no non-empty set; with an empty set it reaches
-            // keyBy as a null key, where Flink throws
-            if (s == 0) atomicOr(&words[0], kErrNullKey);
+            // keyBy as a null key, where Flink throws -- unless the caller keys by something else
+            // and keeps the objIDs in a HashMap, which admits the null key (GEOHIP_TRAJ_NULL_KEY)
+            if (s == 0) {
+                if (null_key) slot = kNullSlot;
+                else atomicOr(&words[0], kErrNullKey);
+            }
         } else {
             const uint64_t b = o0 & kOffMask, e = o1 & kOffMask;
             if (e < b || (e > b && !oid.text)) {
@@ -161,6 +169,12 @@ __global__ void __launch_bounds__(kTB) traj_insert(Strs oid, unsigned n, Strs se
         }
         traj_of[i] = slot;
     }
+    // the null trajectory's representative: indices ascend with the lane, so a wave's lowest null
+    // lane holds its smallest, and it writes only while it would lower the word
+    const unsigned long long nulls = __ballot(slot == kNullSlot);
+    if (nulls && (threadIdx.x & 63u) == (unsigned)(__ffsll((long long)nulls) - 1) &&
+        i < __hip_atomic_load(&words[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMin(&words[3], i);
     // the selected count: one add per workgroup (every wave adding to the one word costs more than
     // the rest of the kernel)
     const int c = __syncthreads_count(slot != kNone);
@@ -169,25 +183,27 @@ __global__ void __launch_bounds__(kTB) traj_insert(Strs oid, unsigned n, Strs se
 
 // flag[i] = point i is its trajectory's first appearance (i <= n; flag[n] = 0 carries the total
 // through the exclusive scan).
-__global__ void __launch_bounds__(kTB) traj_flag(const unsigned* traj_of, const unsigned* tab, unsigned n, unsigned* flag) {
+__global__ void __launch_bounds__(kTB) traj_flag(const unsigned* traj_of, const unsigned* tab, const unsigned* words,
+                                                 unsigned n, unsigned* flag) {
     const unsigned i = blockIdx.x * kTB + threadIdx.x;
     if (i > n) return;
     unsigned f = 0;
     if (i < n) {
         const unsigned slot = traj_of[i];
-        f = slot != kNone && tab[slot] == i;
+        f = slot != kNone && (slot == kNullSlot ? words[3] : tab[slot]) == i;
     }
     flag[i] = f;
 }
 
-__global__ void __launch_bounds__(kTB) traj_finalize(unsigned* traj_of, const unsigned* tab, const unsigned* rank, unsigned n,
-                                                     unsigned T, unsigned* traj_first, unsigned* key, unsigned* val) {
+__global__ void __launch_bounds__(kTB) traj_finalize(unsigned* traj_of, const unsigned* tab, const unsigned* words,
+                                                     const unsigned* rank, unsigned n, unsigned T, unsigned* traj_first,
+                                                     unsigned* key, unsigned* val) {
     const unsigned i = blockIdx.x * kTB + threadIdx.x;
     if (i >= n) return;
     const unsigned slot = traj_of[i];
     unsigned k = T;
     if (slot != kNone) {
-        const unsigned first = tab[slot];
+        const unsigned first = slot == kNullSlot ? words[3] : tab[slot];
         const unsigned t = rank[first];
         traj_of[i] = t;
         if (t < T) {
@@ -441,7 +457,7 @@ int scratch(geohip_ctx* ctx, TSlot slot, size_t bytes, T** out) {
 }
 
 int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oid_off, uint64_t n,
-                    const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint64_t hmask, uint32_t* traj_of,
+                    const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint64_t hmask, uint32_t flags, uint32_t* traj_of,
                     uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm, uint64_t cap_traj, uint64_t* n_traj,
                     uint64_t* n_sel) {
     int rc = ctx_begin(ctx);
@@ -450,6 +466,7 @@ int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oi
     *n_traj = 0;
     *n_sel = 0;
     if (ctx_mem(ctx) != GEOHIP_MEM_DEVICE) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_traj_group takes device memory");
+    if (flags & ~(uint32_t)GEOHIP_TRAJ_NULL_KEY) return ctx_fail(ctx, GEOHIP_ERR_ARG, "unknown flag");
     if (n > kMaxPoints || s > kMaxPoints) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "more than 2^30 points or set entries");
     if (!traj_off || (n && (!oid_off || !traj_of || !perm)) || (s && !set_off))
         return ctx_fail(ctx, GEOHIP_ERR_ARG, "null argument");
@@ -482,14 +499,15 @@ int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oi
     const Strs set{set_text, reinterpret_cast<const unsigned long long*>(set_off)};
     TCHK(hipMemsetAsync(tab, 0xff, ((size_t)mask + 1) * 4, st));
     TCHK(hipMemsetAsync(words, 0, 64, st));
+    TCHK(hipMemsetAsync(words + 3, 0xff, 4, st));
     if (ss) {
         TCHK(hipMemsetAsync(set_tab, 0xff, ((size_t)set_mask + 1) * 4, st));
         tlaunch(ctx, traj_set_build, dim3(blocks_for(s)), dim3(kTB), 0, st, set, ss, set_tab, set_mask, hmask, words);
     }
     tlaunch(ctx, traj_insert, dim3(blocks_for(n)), dim3(kTB), 0, st, oid, nn, set, ss, set_tab, set_mask, tab, mask, hmask,
-            traj_of, words);
+            (unsigned)(flags & GEOHIP_TRAJ_NULL_KEY), traj_of, words);
     unsigned* flag = key;  // dead once scanned
-    tlaunch(ctx, traj_flag, dim3(blocks_for(n + 1)), dim3(kTB), 0, st, traj_of, tab, nn, flag);
+    tlaunch(ctx, traj_flag, dim3(blocks_for(n + 1)), dim3(kTB), 0, st, traj_of, tab, (const unsigned*)words, nn, flag);
     size_t tb = temp_bytes;
     TCHK(rocprim::exclusive_scan(temp, tb, flag, rank, 0u, n + 1, rocprim::plus<unsigned>(), st));
     uint64_t* pin = ctx_pinned(ctx);
@@ -506,7 +524,8 @@ int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oi
     *n_sel = nsel;
     if (T > cap_traj) return ctx_fail(ctx, GEOHIP_ERR_CAPACITY, "cap_traj too small; *n_traj = required");
     if (T && !traj_first) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null traj_first");
-    tlaunch(ctx, traj_finalize, dim3(blocks_for(n)), dim3(kTB), 0, st, traj_of, tab, rank, nn, T, traj_first, key, val);
+    tlaunch(ctx, traj_finalize, dim3(blocks_for(n)), dim3(kTB), 0, st, traj_of, tab, (const unsigned*)words, rank, nn, T, traj_first,
+            key, val);
     unsigned bits = 1;
     while (bits < 32 && (1ull << bits) <= T) bits++;  // keys 0..T
     unsigned* sorted = nsel == nn ? perm : val2;
@@ -539,7 +558,15 @@ int geohip_traj_group(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* 
                       const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint32_t* traj_of,
                       uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm, uint64_t cap_traj, uint64_t* n_traj,
                       uint64_t* n_sel) {
-    return traj_group_impl(ctx, oid_text, oid_off, n, set_text, set_off, s, ~0ull, traj_of, traj_first, traj_off, perm,
+    return traj_group_impl(ctx, oid_text, oid_off, n, set_text, set_off, s, ~0ull, 0, traj_of, traj_first, traj_off, perm,
+                           cap_traj, n_traj, n_sel);
+}
+
+int geohip_traj_group_flags(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oid_off, uint64_t n,
+                            const uint8_t* set_text, const uint64_t* set_off, uint64_t s, uint32_t* traj_of,
+                            uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm, uint64_t cap_traj, uint64_t* n_traj,
+                            uint64_t* n_sel, uint32_t flags) {
+    return traj_group_impl(ctx, oid_text, oid_off, n, set_text, set_off, s, ~0ull, flags, traj_of, traj_first, traj_off, perm,
                            cap_traj, n_traj, n_sel);
 }
 
@@ -550,7 +577,7 @@ int geohip_debug_traj_group_masked(geohip_ctx* ctx, uint64_t hash_mask, const ui
                                    uint64_t n, const uint8_t* set_text, const uint64_t* set_off, uint64_t s,
                                    uint32_t* traj_of, uint32_t* traj_first, uint32_t* traj_off, uint32_t* perm,
                                    uint64_t cap_traj, uint64_t* n_traj, uint64_t* n_sel) {
-    return traj_group_impl(ctx, oid_text, oid_off, n, set_text, set_off, s, hash_mask, traj_of, traj_first, traj_off, perm,
+    return traj_group_impl(ctx, oid_text, oid_off, n, set_text, set_off, s, hash_mask, 0, traj_of, traj_first, traj_off, perm,
                            cap_traj, n_traj, n_sel);
 }
 

@@ -376,6 +376,67 @@ class PointPolygonTRangeQuery(_TrajOperator):
         return [(ids[t], xy[o[t]:o[t + 1]]) for t in range(h["n_traj"])]
 
 
+class PointTAggregateQuery(_TrajOperator):
+    """PointTAggregateQuery.run, window form (tAggregate/PointTAggregateQuery.java:63-99 +
+    TAggregateQuery.java:514-613; the count window's :397-493 is the same loop): keyed by grid
+    cell, per objID in the cell the time between its earliest and latest point.  Returns per
+    emitted cell (gridID "%05d%05d", number of objIDs, map), cells in ascending (cx, cy) order:
+
+    ``ALL`` and any unknown name: {objID: length} of every objID (None: the null objID, a HashMap
+    key like any other); ``SUM`` / ``AVG``: {"": value}, only for cells with sum > 0; ``MIN`` /
+    ``MAX``: {objID: length} of the extreme, only where a second point of some objID set one.
+    Names compare as equalsIgnoreCase does.  The RealTime form (:53-377) reads the wall clock and
+    keeps state across records: GeohipUnsupportedError."""
+
+    def __init__(self, conf: QueryConfiguration, index: Optional[UniformGrid] = None,
+                 ctx: Optional[_abi.Context] = None):
+        if conf.query_type == QueryType.RealTime:
+            raise _abi.GeohipUnsupportedError("PointTAggregateQuery: the RealTime form depends on the wall clock "
+                                              "(TAggregateQuery.java:53-377); only the window form is evaluated")
+        super().__init__(conf, index, ctx)
+
+    def run(self, window: TrajectoryWindow, aggregate_function: str, window_type: str = "TIME"):
+        # window_type picks TimeWindowProcessFunction or CountWindowProcessFunction: one loop
+        self._check_type()  # RealTime was refused by the constructor
+        if self.index is None:
+            raise _abi.GeohipArgumentError("PointTAggregateQuery needs the grid that assigned the cells")
+        ctx = self._ctx()
+        fn = _ascii_upper(str(aggregate_function))
+        g = ctx.traj_group(window.oid_text, window.oid_off, null_key=True)
+        r = ctx.tagg_cells(self.index.abi(), window.x, window.y, window.ts, g, visits=fn not in ("SUM", "AVG", "MIN", "MAX"))
+        keys = ["%05d%05d" % (cx, cy) for cx, cy in r["cell_xy"].cpu().tolist()]
+        count = r["count"].cpu().tolist()
+        if fn in ("SUM", "AVG"):
+            total, val = r["sum"].cpu().tolist(), r["sum" if fn == "SUM" else "avg"].cpu().tolist()
+            return [(keys[c], count[c], {"": val[c]}) for c in range(len(keys)) if total[c] > 0]
+        if fn in ("MIN", "MAX"):
+            length, pt = r[fn.lower()].cpu().tolist(), r[fn.lower() + "_pt"].cpu().tolist()
+            ids = self._obj_ids_or_null(window, [p for p in pt if p >= 0])
+            hit = iter(ids)
+            return [(keys[c], count[c], {next(hit): length[c]}) for c in range(len(keys)) if pt[c] >= 0]
+        off, vt, vl = r["visit_off"].cpu().tolist(), r["visit_traj"].cpu().tolist(), r["visit_len"].cpu().tolist()
+        ids = self._obj_ids_or_null(window, g["traj_first"].cpu().tolist())
+        return [(keys[c], count[c], {ids[vt[v]]: vl[v] for v in range(off[c], off[c + 1])}) for c in range(len(keys))]
+
+    @staticmethod
+    def _obj_ids_or_null(window: TrajectoryWindow, points) -> list:
+        """The objID of each listed point: a str, or None where bit 63 of its offset is set."""
+        off = window.oid_off.cpu().numpy().view(np.uint64)
+        text = window.oid_text.cpu().numpy().tobytes()
+        m = (1 << 63) - 1
+        return [None if int(off[i]) >> 63 else text[int(off[i]) & m:int(off[i + 1]) & m].decode("utf-8", "replace")
+                for i in points]
+
+
+def _ascii_upper(s: str) -> str:
+    """a-z upper-cased, every other character kept: against the ASCII constants "ALL", "SUM", ... this
+    decides as String.equalsIgnoreCase does, which compares char by char (str.upper() would turn
+    "\u00df" into "SS"; U+017F, U+0131 and U+0130, which Java's per-char case folding equates with S
+    and I, are mapped as Java decides them)."""
+    return "".join(chr(ord(c) - 32) if "a" <= c <= "z" else {"\u017f": "S", "\u0131": "I", "\u0130": "I"}.get(c, c)
+                   for c in s)
+
+
 def _rings(polys):
     """(poly_rings, ring_off, vx, vy) of a polygon list: polygon i = rings
     [poly_rings[i], poly_rings[i+1]), ring j = vertices [ring_off[j], ring_off[j+1])."""
