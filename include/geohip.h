@@ -29,7 +29,9 @@
  *   geohip_traj_filter_hit <- its window join back to the whole trajectories   :140-177
  *   geohip_tagg_cells  <- PointTAggregateQuery's window function    spatialOperators/tAggregate/PointTAggregateQuery.java:63-99,
  *                                                                      tAggregate/TAggregateQuery.java:397-493, 514-613
- *   geohip_grid        <- UniformGrid getters                      spatialIndices/UniformGrid.java:136-146
+ *   geohip_tjoin_pp    <- PointPointTJoinQuery.windowBased           spatialOperators/tJoin/PointPointTJoinQuery.java:183-338,
+ *                                                                      tJoin/TJoinQuery.java:158-211
+ *   geohip_grid       <- UniformGrid getters                      spatialIndices/UniformGrid.java:136-146
  *                         (values copied from the Java object, so both constructors :47-85 are covered)
  *
  * Semantics (bit-exact contract, DESIGN.md "Parity"):
@@ -630,6 +632,49 @@ int geohip_tagg_cells(geohip_ctx* ctx, const geohip_grid* grid, const double* x,
                       uint32_t* cell_min_pt, int64_t* cell_max, uint32_t* cell_max_pt, uint32_t* visit_off /* nullable */,
                       uint32_t* visit_traj /* nullable */, int64_t* visit_len /* nullable */, uint64_t* n_cells,
                       uint64_t* n_visits, uint64_t* n_odd);
+
+/* ---- trajectory join (PointPointTJoinQuery, window form) --------------------------------- */
+/* Which trajectories of an ordinary window come within r of which trajectories of a query window
+   (spatialOperators/tJoin/PointPointTJoinQuery.java:183-338 over one grid for both streams).  The
+   real-time form (:66-180) emits the first tuple in join order and runSingle (:341-410) compares
+   objIDs by reference; neither is evaluated.
+   The window form, restated:
+     - every point of either window is keyed by objID (TJoinQuery.java:158-192); a trajectory exists
+       when its objID has MORE than one point in its window (:184; two identical points count);
+     - each query point q is replicated into uGrid.getNeighboringCells(r, q) (TJoinQuery.java:195-211,
+       UniformGrid.java:261-293): the valid cells of the square of Lc = (int)ceil(r / l) layers around
+       q's unclipped cell, with Java's int wrapping; r == 0 means every cell;
+     - an ordinary point p meets a replica when p's cell key equals the replica's cell, so a point
+       outside the grid meets nothing (a NaN coordinate is index 0, as everywhere);
+     - the pair joins when sqrt((q.y - p.y)*(q.y - p.y) + (q.x - p.x)*(q.x - p.x)) <= r
+       (utils/DistanceFunctions.java:60-63: no FMA, a correctly rounded square root, the comparison on
+       the root).  This is NOT geohip_join_pp's predicate (JTS point.distance = Math.hypot): the two
+       distances differ by an ulp in about one pair of eight, either way;
+     - the stages after the join keep only the objIDs of a hit (:246-337), so the window's result is
+       the SET of (ordinary trajectory, query trajectory) with some joining point pair.
+   Inputs (device): each window's x / y (na, nb entries) and its geohip_traj_group result, traj_of
+   (one entry per point) and traj_off (n_traj + 1).  min_points = 2 is the reference; a trajectory
+   takes part when traj_off gives it >= min_points points.  Points with traj_of == 0xffffffff (a
+   group built under a trajIDSet) take no part, not even in the error cases below: the reference
+   has no such filter, this is how the call composes with geohip_traj_group's.  A null objID is the
+   grouping call's error (Flink's null key), not this call's.
+   Output (device): the distinct pairs, out_tpairs[2i] = ta, out_tpairs[2i + 1] = tb, ascending by
+   (ta, tb) (the reference's order is a HashMap's); *out_count (host) = their number.
+   GEOHIP_ERR_CAPACITY when cap is short: *out_count = the needed size, out_tpairs untouched.
+   GEOHIP_ERR_ARG: a traj_of entry >= its n_traj (no such entry is used); r with Lc <= 0 (negative,
+   NaN: the reference exits, UniformGrid.java:272-276), whatever nb; a selected query point whose
+   square is not empty and has the upper index Integer.MAX_VALUE on an axis (r = +infinity with a
+   point in cell (0, 0): the reference's loop never ends) or whose cell key does not parse
+   (NumberFormatException, as for geohip_join_pp).  nb == 0 returns no pair.
+   GEOHIP_ERR_UNSUPPORTED: the bounding rectangle of the occupied cells holds 2^32 - 1 cells or more,
+   or the distinct pairs exceed 2^29.
+   Everything is ordered on the ctx stream; the call reads back once for the checks and the
+   occupied rectangle and once per probe pass for the pass's distinct count.  Device memory only;
+   na, nb, nta, ntb <= 2^30. */
+int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, const double* ay, uint64_t na,
+                    const uint32_t* traj_of_a, const uint32_t* traj_off_a, uint64_t nta, const double* bx,
+                    const double* by, uint64_t nb, const uint32_t* traj_of_b, const uint32_t* traj_off_b, uint64_t ntb,
+                    double r, uint32_t min_points, uint32_t* out_tpairs, uint64_t cap, uint64_t* out_count);
 
 /* ---- host-side planning introspection (no device needed) ------------------------------ */
 /* Query-cell sets of a point query as rectangles: point in G iff in any g rect; point in C

@@ -276,6 +276,11 @@ _SIGS = {
                                        POINTER(c_uint64), POINTER(c_uint64)]),
     "geohip_tagg_cells": (c_int, [_P, POINTER(Grid), _P, _P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P, _P, _P, _P, _P,
                                   _P, _P, _P, _P, _P, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    "geohip_tjoin_pp": (c_int, [_P, POINTER(Grid), _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, c_uint64, _P, _P, c_uint64,
+                                c_double, c_uint32, _P, c_uint64, POINTER(c_uint64)]),
+    "geohip_debug_tjoin": (c_int, [_P, c_uint64, c_uint64]),
+    "geohip_debug_tjoin_cell_budget": (c_int, [_P, c_uint64]),
+    "geohip_debug_tjoin_passes": (c_int, [_P, POINTER(c_uint64)]),
     "geohip_debug_trange_cell_budget": (c_int, [_P, c_uint64]),
     "geohip_debug_selftest_fp64": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, _P]),
     "geohip_debug_classify": (c_int, [POINTER(Grid), c_double, c_double, c_double, _P, _P, c_uint64, _P]),
@@ -1322,6 +1327,70 @@ class Context:
         if visits:
             out.update(visit_off=voff[:C + 1], visit_traj=vtr[:V], visit_len=vlen[:V])
         return out
+
+    # ---- trajectory join ----------------------------------------------------------------------
+    def debug_tjoin(self, table_slots: int = 0, hash_mask: int = 0xFFFFFFFFFFFFFFFF, cell_budget: int = 0):
+        """Test hooks of tjoin_pp: ``table_slots`` forces the hash set's first size (0 = the sizing
+        policy), every hash is ANDed with ``hash_mask`` (0: one probe chain), ``cell_budget`` bounds
+        the cell-start table (0 = the default; below the occupied rectangle the spans are found by
+        search).  The defaults restore the product behaviour."""
+        self._check(lib.geohip_debug_tjoin(self.h, int(table_slots), int(hash_mask)), "debug_tjoin")
+        self._check(lib.geohip_debug_tjoin_cell_budget(self.h, int(cell_budget)), "debug_tjoin_cell_budget")
+
+    def debug_tjoin_passes(self) -> int:
+        """Probe passes tjoin_pp has run on this ctx (one per call unless the hash set regrew)."""
+        out = c_uint64(0)
+        self._check(lib.geohip_debug_tjoin_passes(self.h, ctypes.byref(out)), "debug_tjoin_passes")
+        return out.value
+
+    def tjoin_pp(self, grid: Grid, ax, ay, group_a, bx, by, group_b, r, min_points=2, cap=None):
+        """geohip_tjoin_pp (x / y float64 device tensors of the ordinary (a) and the query (b)
+        window, each with its ``traj_group`` result): the windowed PointPointTJoinQuery as the
+        distinct (ordinary trajectory, query trajectory) pairs with some point pair within ``r``
+        under sqrt(dy*dy + dx*dx) <= r, both trajectories of at least ``min_points`` points.
+        Returns an int32 [m, 2] tensor ascending by (ta, tb).  ``cap`` None: two-phase on the
+        capacity error; otherwise GeohipCapacityError carries ``count``."""
+        import torch
+        self._dev(ax, "ax")
+        self._dev(ay, "ay")
+        self._dev(bx, "bx")
+        self._dev(by, "by")
+        na, nb = ax.numel(), bx.numel()
+        of_a, off_a, of_b, off_b = group_a["traj_of"], group_a["traj_off"], group_b["traj_of"], group_b["traj_off"]
+        for t, name in ((of_a, "traj_of_a"), (off_a, "traj_off_a"), (of_b, "traj_of_b"), (off_b, "traj_off_b")):
+            self._dev(t, name, "int32")
+        nta, ntb = int(group_a["n_traj"]), int(group_b["n_traj"])
+        if ay.numel() != na or of_a.numel() != na or by.numel() != nb or of_b.numel() != nb:
+            raise GeohipArgumentError("tjoin_pp: a window's x, y and traj_of differ in length")
+        if off_a.numel() != nta + 1 or off_b.numel() != ntb + 1:
+            raise GeohipArgumentError("tjoin_pp: traj_off needs n_traj + 1 entries")
+        if self._mem != MEM_DEVICE:
+            self.set_mem(MEM_DEVICE)
+        cnt = c_uint64(0)
+
+        def call(out, room):
+            return lib.geohip_tjoin_pp(self.h, ctypes.byref(grid), ax.data_ptr(), ay.data_ptr(), na, of_a.data_ptr(),
+                                       off_a.data_ptr(), nta, bx.data_ptr(), by.data_ptr(), nb, of_b.data_ptr(),
+                                       off_b.data_ptr(), ntb, float(r), int(min_points),
+                                       out.data_ptr() if out is not None else None, room, ctypes.byref(cnt))
+
+        # cap None: room for every pair while that is small (one call), else learn the size first
+        room = min(nta * ntb, 1 << 22) if cap is None else int(cap)
+        out = torch.empty(2 * room, dtype=torch.int32, device=ax.device) if room else None
+        rc = call(out, room)
+        if rc == ERR_CAPACITY and cap is None:
+            room = cnt.value
+            out = torch.empty(2 * room, dtype=torch.int32, device=ax.device)
+            rc = call(out, room)
+        if rc == ERR_CAPACITY:
+            err = GeohipCapacityError(f"tjoin_pp: {lib.geohip_last_error(self.h).decode(errors='replace')}")
+            err.count = cnt.value
+            raise err
+        self._check(rc, "tjoin_pp")
+        m = cnt.value
+        if out is None or m == 0:
+            return torch.empty((0, 2), dtype=torch.int32, device=ax.device)
+        return out[:2 * m].view(-1, 2)
 
     def synth_uniform_async(self, x, y, base, seed, bbox):
         self._dev(x, "x")

@@ -37,6 +37,7 @@ SOURCES = {
     "traj.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "trange.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
     "tagg.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
+    "tjoin.hip": ["-x", "hip", f"--offload-arch={ARCH}"],
 }
 
 

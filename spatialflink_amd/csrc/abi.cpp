@@ -136,6 +136,9 @@ struct geohip_ctx {
     void* pcache = nullptr;          // point-polygon plan cache (cell_kernels.hip owns the type)
     void* kcache = nullptr;          // point-polygon kNN polygon cache (cell_kernels.hip owns the type)
     void* tcache = nullptr;          // trajectory range polygon plan and device tables (trange.hip owns the type)
+    // trajectory join test knobs and counter (tjoin.hip): forced first table size (0: its policy),
+    // hash mask, cell budget (0: its default), probe passes run
+    uint64_t tjoin_dbg[4] = {0, ~0ull, 0, 0};
 };
 
 namespace {
@@ -1417,6 +1420,7 @@ int ctx_fault_block(geohip_ctx* ctx, unsigned** out) {
 void** ctx_pcache_slot(geohip_ctx* ctx) { return &ctx->pcache; }
 void** ctx_kcache_slot(geohip_ctx* ctx) { return &ctx->kcache; }
 void** ctx_tcache_slot(geohip_ctx* ctx) { return &ctx->tcache; }
+uint64_t* ctx_tjoin_debug(geohip_ctx* ctx) { return ctx->tjoin_dbg; }
 void ctx_timing_events(geohip_ctx* ctx, hipEvent_t* e0, hipEvent_t* e1) { timing_events(ctx, e0, e1); }
 void ctx_kernel_events(geohip_ctx* ctx, hipEvent_t* e0, hipEvent_t* e1) { timed_pair(ctx, e0, e1, 1); }
 void ctx_kernel_step_events(geohip_ctx* ctx, hipEvent_t* e0, hipEvent_t* e1) { timed_pair(ctx, e0, e1, 2); }

@@ -59,6 +59,9 @@ int ctx_stage_xy(geohip_ctx* ctx, const double* x, const double* y, uint64_t n, 
                  const double** dy);
 void** ctx_pcache_slot(geohip_ctx* ctx);  // the ctx's point-polygon plan cache (owned by cell_kernels)
 void** ctx_kcache_slot(geohip_ctx* ctx);  // the ctx's point-polygon kNN polygon cache
+// trajectory join (tjoin.hip) test knobs: [0] first table slots (0: the sizing policy), [1] hash
+// mask, [2] cell budget (0: the default), [3] probe passes run on this ctx
+uint64_t* ctx_tjoin_debug(geohip_ctx* ctx);
 
 // squared-distance screen bounds for "dist <= r" (r2lo < 0 / r2hi = inf where they cannot hold)
 void pp_screen_bounds(double r, double* r2lo, double* r2hi);

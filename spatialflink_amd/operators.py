@@ -16,6 +16,7 @@ MI355X through libgeohip:
 ``PointTStatsQuery.run`` (window)     ``spatialOperators/tStats/PointTStatsQuery.java:64-92``, ``TStatsQuery.java:148-189``
 ``PointTFilterQuery.run``             ``spatialOperators/tFilter/PointTFilterQuery.java:30-118``
 ``PointPolygonTRangeQuery.run``       ``spatialOperators/tRange/PointPolygonTRangeQuery.java:53-177``
+``PointPointTJoinQuery.run`` (window) ``spatialOperators/tJoin/PointPointTJoinQuery.java:183-338``, ``TJoinQuery.java:158-211``
 ====================================  =========================================================
 
 Window contents are columnar (``PointWindow``: x, y and optional object ids); results are
@@ -426,6 +427,65 @@ class PointTAggregateQuery(_TrajOperator):
         m = (1 << 63) - 1
         return [None if int(off[i]) >> 63 else text[int(off[i]) & m:int(off[i + 1]) & m].decode("utf-8", "replace")
                 for i in points]
+
+
+class PointPointTJoinQuery(_TrajOperator):
+    """PointPointTJoinQuery.run, window form (tJoin/PointPointTJoinQuery.java:183-338 +
+    TJoinQuery.java:158-211): which trajectories of the ordinary window come within
+    ``join_distance`` of which trajectories of the query window, both on the operator's grid.  A
+    query point is replicated into its neighbouring cells, an ordinary point meets the replicas
+    of its own cell, and a pair joins when sqrt(dy*dy + dx*dx) <= join_distance
+    (DistanceFunctions.java:60-63, not JTS ``distance``); the stages after the join keep only the
+    objIDs.  Returns [((objID_a, coords_a [k, 2]), (objID_b, coords_b [k', 2]))] for every pair of
+    objIDs with a joining point pair where both have more than one point in their window
+    (TJoinQuery.java:184), coordinates in arrival order, pairs ascending by (ordinary trajectory,
+    query trajectory) in order of the objIDs' first appearance (the reference's order is a
+    HashMap's).  Every point of either window is keyed by objID, so a null objID raises.
+
+    Not evaluated: the RealTime form (:66-180), whose output carries ``firstPoint``, the first tuple
+    in join order (GeohipUnsupportedError at construction); and ``runSingle`` (:341-410), which
+    tells a trajectory from itself by ``!=`` on String references (:370)."""
+
+    def __init__(self, conf: QueryConfiguration, index: Optional[UniformGrid] = None,
+                 ctx: Optional[_abi.Context] = None):
+        if conf.query_type == QueryType.RealTime:
+            raise _abi.GeohipUnsupportedError("PointPointTJoinQuery: the RealTime form emits the first tuple in join "
+                                              "order (PointPointTJoinQuery.java:66-180); only the window form is evaluated")
+        super().__init__(conf, index, ctx)
+
+    def runSingle(self, *args, **kwargs):
+        raise _abi.GeohipUnsupportedError("PointPointTJoinQuery.runSingle compares objIDs by String reference "
+                                          "(PointPointTJoinQuery.java:370); it is not evaluated")
+
+    def run(self, ordinary: TrajectoryWindow, query: TrajectoryWindow, join_distance: float):
+        self._check_type()  # RealTime was refused by the constructor
+        if self.index is None:
+            raise _abi.GeohipArgumentError("PointPointTJoinQuery needs the grid that assigned the cells")
+        ctx = self._ctx()
+        ga, gb = self._group(ordinary, ()), self._group(query, ())  # an empty set: a null objID raises
+        pairs = ctx.tjoin_pp(self.index.abi(), ordinary.x, ordinary.y, ga, query.x, query.y, gb, float(join_distance))
+        if pairs.numel() == 0:
+            return []
+        p = pairs.cpu().numpy()
+        side_a = self._trajectories(ctx, ordinary, ga, np.unique(p[:, 0]))
+        side_b = self._trajectories(ctx, query, gb, np.unique(p[:, 1]))
+        return [(side_a[int(ta)], side_b[int(tb)]) for ta, tb in p]
+
+    def _trajectories(self, ctx, window: TrajectoryWindow, g, which) -> dict:
+        """{t: (objID, coords [k, 2])} of the listed trajectories of a group: one gather."""
+        import torch
+        off = g["traj_off"].cpu().numpy().astype(np.int64)
+        pos = np.concatenate([np.arange(off[t], off[t + 1]) for t in which])
+        sub = g["perm"][torch.from_numpy(pos).to(g["perm"].device)].contiguous()
+        gx, gy = ctx.traj_gather(window.x, window.y, sub)
+        xy = np.stack([gx.cpu().numpy(), gy.cpu().numpy()], axis=1)
+        ids = self._obj_ids(window, g["traj_first"][torch.from_numpy(np.asarray(which, dtype=np.int64)).to(g["perm"].device)])
+        out, at = {}, 0
+        for t, oid in zip(which, ids):
+            k = int(off[t + 1] - off[t])
+            out[int(t)] = (oid, xy[at:at + k])
+            at += k
+        return out
 
 
 def _ascii_upper(s: str) -> str:
