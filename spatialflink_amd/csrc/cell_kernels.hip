@@ -697,10 +697,6 @@ __device__ __forceinline__ void pairs_end(uint2* buf, unsigned long long& cnt, u
 }
 
 // ------------------------------------------------------------------ join -----------------
-struct QRect {
-    int32_t x0, x1, y0, y1;  // key space, clipped; x0 > x1 = empty
-};
-
 __device__ __forceinline__ bool rect_tiles(const QRect& R, const TileGeom& g, int32_t& tx0, int32_t& tx1, int32_t& ty0,
                                            int32_t& ty1) {
     if (R.x0 > R.x1 || R.y0 > R.y1) return false;
@@ -713,53 +709,9 @@ __device__ __forceinline__ bool rect_tiles(const QRect& R, const TileGeom& g, in
 
 // Query blocks on the device (PointPointJoinQuery.java:113-150 with JoinQuery.
 // getReplicatedPointQueryStream, JoinQuery.java:73-90, and UniformGrid.getNeighboringCells,
-// UniformGrid.java:261-293): the query's cell on the query grid, its key's round trip through
-// HelperClass.getIntCellIndices when the key is not 10 characters, the int-wrapping
-// [c - Lc, c + Lc] loops, clipped to the key space.  err: 1 = NumberFormatException,
-// 2 = a loop that never terminates (the host reports GEOHIP_ERR_ARG); the query stays empty.
-__device__ __forceinline__ int d_format05(int32_t v, char* out) {
-    char digits[12];
-    int nd = 0;
-    int64_t a = v;
-    const bool neg = a < 0;
-    if (neg) a = -a;
-    do {
-        digits[nd++] = (char)('0' + (int)(a % 10));
-        a /= 10;
-    } while (a != 0);
-    const int width = nd + (neg ? 1 : 0);
-    int p = 0;
-    if (neg) out[p++] = '-';
-    for (int i = width; i < 5; i++) out[p++] = '0';
-    while (nd > 0) out[p++] = digits[--nd];
-    return p;
-}
-// Integer.parseInt(s.replaceFirst("^0+(?!$)", ""))
-__device__ __forceinline__ bool d_java_parse(const char* s, int len, int32_t* out) {
-    int skip = 0;
-    while (skip < len - 1 && s[skip] == '0') skip++;
-    s += skip;
-    len -= skip;
-    if (len <= 0) return false;
-    bool neg = false;
-    int p = 0;
-    if (s[0] == '+' || s[0] == '-') {
-        if (len == 1) return false;
-        neg = s[0] == '-';
-        p = 1;
-    }
-    int64_t v = 0;
-    for (; p < len; p++) {
-        if (s[p] < '0' || s[p] > '9') return false;
-        v = v * 10 + (s[p] - '0');
-        if (v > 2147483648LL) return false;
-    }
-    if (neg) v = -v;
-    if (v > INT32_MAX || v < INT32_MIN) return false;
-    *out = (int32_t)v;
-    return true;
-}
-
+// UniformGrid.java:261-293): the query's cell on the query grid and its neighbour square in the
+// key space (d_neighbor_square, locate.h).  err: 1 = NumberFormatException, 2 = a loop that never
+// terminates (the host reports GEOHIP_ERR_ARG); the query stays empty.
 struct JqGeom {
     double mnx, mny, l;  // query grid
     int32_t nb, lc;      // key space side, candidate layers
@@ -774,34 +726,10 @@ __global__ __launch_bounds__(kTB) void jq_rect(const double* __restrict__ qx, co
     if (i >= nq) return;
     QRect R{0, g.nb - 1, 0, g.nb - 1};
     if (!g.all_cells) {
-        const int32_t cx = d_axis_cell(qx[i], g.mnx, g.l), cy = d_axis_cell(qy[i], g.mny, g.l);
-        int32_t ci = cx, cj = cy;
-        bool ok = true;
-        if (!(cx >= -9999 && cx <= 99999 && cy >= -9999 && cy <= 99999)) {
-            char key[24];
-            int n = d_format05(cx, key);
-            n += d_format05(cy, key + n);
-            ok = d_java_parse(key, 5, &ci) && d_java_parse(key + 5, n - 5, &cj);
-        }
-        if (!ok) {
-            atomicMax(err, 1u);
-            if (fault) atomicOr(fault, kFaultQueryKey);
-            R = QRect{1, 0, 1, 0};
-        } else {
-            const int32_t lo_i = (int32_t)(uint32_t)(uint64_t)((int64_t)ci - g.lc);
-            const int32_t hi_i = (int32_t)(uint32_t)(uint64_t)((int64_t)ci + g.lc);
-            const int32_t lo_j = (int32_t)(uint32_t)(uint64_t)((int64_t)cj - g.lc);
-            const int32_t hi_j = (int32_t)(uint32_t)(uint64_t)((int64_t)cj + g.lc);
-            if (lo_i > hi_i || lo_j > hi_j) {
-                R = QRect{1, 0, 1, 0};
-            } else if (hi_i == INT32_MAX || hi_j == INT32_MAX) {
-                atomicMax(err, 2u);
-                if (fault) atomicOr(fault, kFaultQueryLoop);
-                R = QRect{1, 0, 1, 0};
-            } else {
-                R = QRect{lo_i > 0 ? lo_i : 0, hi_i < g.nb - 1 ? hi_i : g.nb - 1, lo_j > 0 ? lo_j : 0,
-                          hi_j < g.nb - 1 ? hi_j : g.nb - 1};
-            }
+        const int st = d_neighbor_square(d_axis_cell(qx[i], g.mnx, g.l), d_axis_cell(qy[i], g.mny, g.l), g.lc, g.nb, R);
+        if (st) {
+            atomicMax(err, (unsigned)st);
+            if (fault) atomicOr(fault, st == 1 ? kFaultQueryKey : kFaultQueryLoop);
         }
     }
     rect[i] = R;
@@ -4231,6 +4159,15 @@ __global__ __launch_bounds__(1024) void topk_take(const unsigned long long* __re
 }
 
 // ================================================================== host side =============
+int check_grid_basic(geohip_ctx* ctx, const geohip_grid* g, const char* what) {  // join.h
+    if (!g) return ctx_fail(ctx, GEOHIP_ERR_ARG, std::string(what) + ": null grid");
+    if (!(g->n > 0) || !(g->cell_len > 0) || !std::isfinite(g->cell_len) || !std::isfinite(g->min_x) ||
+        !std::isfinite(g->min_y))
+        return ctx_fail(ctx, GEOHIP_ERR_ARG, std::string(what) + ": invalid grid");
+    if (g->n > 99999) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, std::string(what) + ": more than 99999 cells per side");
+    return GEOHIP_OK;
+}
+
 namespace {
 
 enum JSlot {
@@ -4256,15 +4193,6 @@ struct Scratch {
         return reinterpret_cast<T*>(p);
     }
 };
-
-int check_grid_basic(geohip_ctx* ctx, const geohip_grid* g, const char* what) {
-    if (!g) return ctx_fail(ctx, GEOHIP_ERR_ARG, std::string(what) + ": null grid");
-    if (!(g->n > 0) || !(g->cell_len > 0) || !std::isfinite(g->cell_len) || !std::isfinite(g->min_x) ||
-        !std::isfinite(g->min_y))
-        return ctx_fail(ctx, GEOHIP_ERR_ARG, std::string(what) + ": invalid grid");
-    if (g->n > 99999) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, std::string(what) + ": more than 99999 cells per side");
-    return GEOHIP_OK;
-}
 
 TileGeom tile_geom(const geohip_grid& g, int32_t nb) {
     TileGeom t;

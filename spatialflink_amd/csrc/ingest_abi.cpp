@@ -17,12 +17,6 @@ using namespace geohip;
 
 namespace {
 
-#define ICHK(expr)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
 enum { I_TEXT, I_STATUS, I_WORDS, I_X, I_Y, I_TS, I_CELL, I_LIST, I_OID, I_OIDLEN, I_OIDSEG };
 
 // java.util.regex metacharacters: "\\s*" + delimiter + "\\s*" would not be a literal split
@@ -142,7 +136,7 @@ int ingest_impl(geohip_ctx* ctx, const geohip_grid* grid, const geohip_ingest_sp
         if (!rc && out_cell) rc = ctx_ensure_ingest(ctx, I_CELL, cap * 4, &pc);
         if (!rc && out_oid) rc = ctx_ensure_ingest(ctx, I_OID, cap * 8, &po);
         if (rc) return rc;
-        if (nbytes) ICHK(hipMemcpyAsync(t, text, nbytes, hipMemcpyHostToDevice, st));
+        if (nbytes) GEOHIP_CHK(hipMemcpyAsync(t, text, nbytes, hipMemcpyHostToDevice, st));
         dtext = static_cast<const uint8_t*>(t);
         dx = static_cast<double*>(px);
         dy = static_cast<double*>(py);
@@ -153,14 +147,14 @@ int ingest_impl(geohip_ctx* ctx, const geohip_grid* grid, const geohip_ingest_sp
     a.oid = doid;
     // [0] total, [1] ticket (re-armed by the kernel), [2] ~first rejected record, [3] listed chunks
     unsigned long long* w = static_cast<unsigned long long*>(words);
-    ICHK(hipMemsetAsync(w + 2, 0, 16, st));
+    GEOHIP_CHK(hipMemsetAsync(w + 2, 0, 16, st));
     const IngestLookback lb{static_cast<unsigned long long*>(status), reinterpret_cast<unsigned*>(w + 1),
                             epoch, static_cast<ulonglong2*>(list), reinterpret_cast<unsigned*>(w + 3)};
     hipError_t e = launch_ingest(ctx, dtext, nbytes, a, lb, w, dx, dy, dts, dcell, cap, w + 2, st);
     if (e != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string("ingest launch: ") + hipGetErrorString(e));
     uint64_t* pinned = ctx_pinned(ctx);
-    ICHK(hipMemcpyAsync(pinned, w, 32, hipMemcpyDeviceToHost, st));
-    ICHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipMemcpyAsync(pinned, w, 32, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     if (pinned[3] >> 32) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, "ingest: record-base look-back gave up");
     const uint64_t total = pinned[0], bad = pinned[2] ? ~pinned[2] : UINT64_MAX;
     *out_count = total;
@@ -168,11 +162,11 @@ int ingest_impl(geohip_ctx* ctx, const geohip_grid* grid, const geohip_ingest_sp
     if (!dev) {
         const uint64_t m = total < cap ? total : cap;
         if (m) {
-            ICHK(hipMemcpy(out_x, dx, m * 8, hipMemcpyDeviceToHost));
-            ICHK(hipMemcpy(out_y, dy, m * 8, hipMemcpyDeviceToHost));
-            if (out_ts) ICHK(hipMemcpy(out_ts, dts, m * 8, hipMemcpyDeviceToHost));
-            if (out_cell) ICHK(hipMemcpy(out_cell, dcell, m * 4, hipMemcpyDeviceToHost));
-            if (out_oid) ICHK(hipMemcpy(out_oid, doid, m * 8, hipMemcpyDeviceToHost));
+            GEOHIP_CHK(hipMemcpy(out_x, dx, m * 8, hipMemcpyDeviceToHost));
+            GEOHIP_CHK(hipMemcpy(out_y, dy, m * 8, hipMemcpyDeviceToHost));
+            if (out_ts) GEOHIP_CHK(hipMemcpy(out_ts, dts, m * 8, hipMemcpyDeviceToHost));
+            if (out_cell) GEOHIP_CHK(hipMemcpy(out_cell, dcell, m * 4, hipMemcpyDeviceToHost));
+            if (out_oid) GEOHIP_CHK(hipMemcpy(out_oid, doid, m * 8, hipMemcpyDeviceToHost));
         }
     }
     if (bad != UINT64_MAX)
@@ -220,15 +214,15 @@ int geohip_ingest_oid_compact(geohip_ctx* ctx, const char* text, uint64_t nbytes
                                       static_cast<uint64_t*>(len), static_cast<uint64_t*>(seg), out_off, nullptr, 0, st);
     if (e != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string("oid compact launch: ") + hipGetErrorString(e));
     uint64_t* pinned = ctx_pinned(ctx);
-    ICHK(hipMemcpyAsync(pinned, static_cast<uint64_t*>(seg) + nseg, 16, hipMemcpyDeviceToHost, st));
-    ICHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipMemcpyAsync(pinned, static_cast<uint64_t*>(seg) + nseg, 16, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     if (pinned[1]) return ctx_fail(ctx, GEOHIP_ERR_ARG, "an objID span lies outside the text");
     *out_len = pinned[0];
     if (pinned[0] > cap) return ctx_fail(ctx, GEOHIP_ERR_CAPACITY, "output capacity too small; *out_len = required");
     e = launch_oid_compact(ctx, reinterpret_cast<const uint8_t*>(text), nbytes, oid_spans, m, static_cast<uint64_t*>(len),
                            static_cast<uint64_t*>(seg), out_off, out_text, cap, st);
     if (e != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string("oid compact launch: ") + hipGetErrorString(e));
-    ICHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     return GEOHIP_OK;
 }
 

@@ -20,7 +20,16 @@ constexpr unsigned kFaultCandNeed = 8u;       // point-polygon: the candidate bu
 
 // context services implemented in abi.cpp
 int ctx_fail(geohip_ctx* ctx, int code, const std::string& msg);
-int ctx_ensure(geohip_ctx* ctx, int slot, size_t bytes, void** out);  // slot 0..27 (JSlot, cell_kernels.hip)
+
+// A HIP call inside a function that has `ctx` and returns a status: its failure is the function's.
+#define GEOHIP_CHK(expr)                                                                                 \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
+    } while (0)
+
+// slot 0..27: JSlot in cell_kernels.hip; the trajectory calls take 0..9 only (kCallSlots, traj_common.h)
+int ctx_ensure(geohip_ctx* ctx, int slot, size_t bytes, void** out);
 int ctx_ensure_zeroed(geohip_ctx* ctx, int slot, size_t bytes, void** out);  // zeroed when (re)allocated
 int ctx_ensure_ingest(geohip_ctx* ctx, int slot, size_t bytes, void** out);  // slot 0..11
 int ctx_ensure_ingest_zeroed(geohip_ctx* ctx, int slot, size_t bytes, void** out);  // zeroed when (re)allocated
@@ -62,6 +71,10 @@ void** ctx_kcache_slot(geohip_ctx* ctx);  // the ctx's point-polygon kNN polygon
 // trajectory join (tjoin.hip) test knobs: [0] first table slots (0: the sizing policy), [1] hash
 // mask, [2] cell budget (0: the default), [3] probe passes run on this ctx
 uint64_t* ctx_tjoin_debug(geohip_ctx* ctx);
+
+// a query's grid: non-null, n in 1..99999, a finite origin and a finite positive cell length
+// (cell_kernels.hip); what names the grid in the message
+int check_grid_basic(geohip_ctx* ctx, const geohip_grid* g, const char* what);
 
 // squared-distance screen bounds for "dist <= r" (r2lo < 0 / r2hi = inf where they cannot hold)
 void pp_screen_bounds(double r, double* r2lo, double* r2hi);

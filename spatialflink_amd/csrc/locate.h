@@ -1,6 +1,7 @@
-// locate.h -- device pieces shared by the polygon kernels (cell_kernels.hip, trange.hip): a
-// point's grid cell, RayCrossingCounter.countSegment with the exact determinant sign, and the
-// y-slab crossing lists of a planned polygon.
+// locate.h -- device pieces shared by the cell kernels (cell_kernels.hip, trange.hip, tagg.hip,
+// tjoin.hip): a point's grid cell, the neighbour square of a join's query point with its cell
+// key's round trip through Java, RayCrossingCounter.countSegment with the exact determinant sign,
+// and the y-slab crossing lists of a planned polygon.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +20,84 @@ __device__ __forceinline__ int32_t d_java_d2i(double v) {
 // HelperClass.assignGridCellID per axis: (int)Math.floor((v - min)/l), exact division.
 __device__ __forceinline__ int32_t d_axis_cell(double v, double mn, double l) {
     return d_java_d2i(__builtin_floor((v - mn) / l));
+}
+
+// A cell key's round trip through Java, as both joins replicate their query points (jq_rect in
+// cell_kernels.hip, tj_qrect in tjoin.hip).  The key is String.format("%05d", cx) +
+// String.format("%05d", cy) (HelperClass.java:54-57, 117-120); getIntCellIndices
+// (HelperClass.java:263-276) splits it after the fifth character and reads each half with
+// Integer.parseInt(s.replaceFirst("^0+(?!$)", "")) (HelperClass.java:60-63).  A cell outside
+// [-9999, 99999] makes a key that is not 10 characters, so the split lands elsewhere.
+__device__ __forceinline__ int d_format05(int32_t v, char* out) {
+    char digits[12];
+    int nd = 0;
+    int64_t a = v;
+    const bool neg = a < 0;
+    if (neg) a = -a;
+    do {
+        digits[nd++] = (char)('0' + (int)(a % 10));
+        a /= 10;
+    } while (a != 0);
+    const int width = nd + (neg ? 1 : 0);
+    int p = 0;
+    if (neg) out[p++] = '-';
+    for (int i = width; i < 5; i++) out[p++] = '0';
+    while (nd > 0) out[p++] = digits[--nd];
+    return p;
+}
+__device__ __forceinline__ bool d_java_parse(const char* s, int len, int32_t* out) {
+    int skip = 0;
+    while (skip < len - 1 && s[skip] == '0') skip++;
+    s += skip;
+    len -= skip;
+    if (len <= 0) return false;
+    bool neg = false;
+    int p = 0;
+    if (s[0] == '+' || s[0] == '-') {
+        if (len == 1) return false;
+        neg = s[0] == '-';
+        p = 1;
+    }
+    int64_t v = 0;
+    for (; p < len; p++) {
+        if (s[p] < '0' || s[p] > '9') return false;
+        v = v * 10 + (s[p] - '0');
+        if (v > 2147483648LL) return false;
+    }
+    if (neg) v = -v;
+    if (v > INT32_MAX || v < INT32_MIN) return false;
+    *out = (int32_t)v;
+    return true;
+}
+
+struct QRect {
+    int32_t x0, x1, y0, y1;  // cells, clipped; x0 > x1 = empty
+};
+
+// UniformGrid.getNeighboringCells (UniformGrid.java:261-293) of a point whose unclipped cell is
+// (cx, cy): the cell indices as its key hands them on, the int-wrapping loops [c - lc, c + lc] on
+// both axes, and of their cells those inside [0, nside - 1].  Returns 0 with R the clipped square
+// (empty where a wrapped loop runs no step); 1 = the key does not parse (NumberFormatException) and
+// 2 = a loop's bound is Integer.MAX_VALUE, so it never ends -- both with R empty.
+__device__ __forceinline__ int d_neighbor_square(int32_t cx, int32_t cy, int32_t lc, int32_t nside, QRect& R) {
+    int32_t ci = cx, cj = cy;
+    bool ok = true;
+    if (!(cx >= -9999 && cx <= 99999 && cy >= -9999 && cy <= 99999)) {
+        char key[24];
+        int n = d_format05(cx, key);
+        n += d_format05(cy, key + n);
+        ok = d_java_parse(key, 5, &ci) && d_java_parse(key + 5, n - 5, &cj);
+    }
+    R = QRect{1, 0, 1, 0};
+    if (!ok) return 1;
+    const int32_t lo_i = (int32_t)(uint32_t)(uint64_t)((int64_t)ci - lc);
+    const int32_t hi_i = (int32_t)(uint32_t)(uint64_t)((int64_t)ci + lc);
+    const int32_t lo_j = (int32_t)(uint32_t)(uint64_t)((int64_t)cj - lc);
+    const int32_t hi_j = (int32_t)(uint32_t)(uint64_t)((int64_t)cj + lc);
+    if (lo_i > hi_i || lo_j > hi_j) return 0;
+    if (hi_i == INT32_MAX || hi_j == INT32_MAX) return 2;
+    R = QRect{lo_i > 0 ? lo_i : 0, hi_i < nside - 1 ? hi_i : nside - 1, lo_j > 0 ? lo_j : 0, hi_j < nside - 1 ? hi_j : nside - 1};
+    return 0;
 }
 
 // Exact sign of x1*y2 - y1*x2 (RobustDeterminant.signOfDet2x2): error-free products by fma,

@@ -45,27 +45,18 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "geohip.h"
-#include "join.h"
-#include "locate.h"
+#include "traj_common.h"
 
 namespace geohip {
 namespace {
 
-constexpr int kTB = 256;
-constexpr int kWaves = kTB / 64;
 constexpr unsigned kChunk = kTB;  // elements per workgroup of the two scans (tests/test_gpu_tagg.py: CHUNK)
-constexpr uint64_t kMaxPoints = 1ull << 30;
 constexpr int32_t kCellLo = -9999, kCellHi = 99999;  // 5 + 5 characters of "%05d%05d" split uniquely
 constexpr long long kLongMax = 0x7fffffffffffffffLL;
 constexpr long long kLongMin = -kLongMax - 1;
-constexpr unsigned kNone = 0xffffffffu;
 
-// scratch slots (ctx_ensure; the call owns them for its own duration on the ctx stream).  Only
-// slots 0..9, as traj.hip: they carry nothing from one call to the next, while higher ones do (slot
-// 10 keeps the point-polygon join's uploaded polygon tables between calls, cell_kernels.hip J_POLY).
-// G_PARTS packs the five per-chunk arrays of the two scans.
+// scratch slots (kCallSlots, traj_common.h).  G_PARTS packs the five per-chunk arrays of the two scans.
 enum GSlot { G_CXY, G_KEY, G_KEY2, G_VAL2, G_TS, G_TR, G_TEMP, G_WORDS, G_PARTS };
-static_assert(G_PARTS <= 9, "scratch slots that no call keeps state in");
 
 // words block: [0] error bits, [1] points whose cell leaves [kCellLo, kCellHi], [2..5] the cell
 // rectangle as maxima of cx - kCellLo, kCellHi - cx, cy - kCellLo, kCellHi - cy, [6] cells, [7] visits
@@ -190,20 +181,10 @@ __device__ __forceinline__ unsigned block_sum_scan(unsigned v, unsigned* sw) {
     return v;
 }
 
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 // ---- 1. cells, checks, rectangle ---------------------------------------------------------------
 __global__ void __launch_bounds__(kTB) tagg_locate(const double* x, const double* y, unsigned n, const unsigned* traj_of,
                                                    unsigned T, const unsigned* perm, unsigned n_sel, double mnx, double mny,
                                                    double l, int2* cxy, unsigned* words) {
-    __shared__ unsigned red[kWaves][6];
     const unsigned j = blockIdx.x * kTB + threadIdx.x;
     unsigned err = 0, odd = 0, hx = 0, lx = 0, hy = 0, ly = 0;
     if (j < n_sel) {
@@ -225,34 +206,9 @@ __global__ void __launch_bounds__(kTB) tagg_locate(const double* x, const double
         }
         cxy[j] = c;
     }
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned werr = __ballot(err) ? 1u : 0u;
     const unsigned wodd = (unsigned)__popcll(__ballot(odd));
-    hx = wave_max(hx);
-    lx = wave_max(lx);
-    hy = wave_max(hy);
-    ly = wave_max(ly);
-    if (lane == 0) {
-        red[wave][0] = werr;
-        red[wave][1] = wodd;
-        red[wave][2] = hx;
-        red[wave][3] = lx;
-        red[wave][4] = hy;
-        red[wave][5] = ly;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned a[6] = {0, 0, 0, 0, 0, 0};
-        for (int w = 0; w < kWaves; w++) {
-            a[0] |= red[w][0];
-            a[1] += red[w][1];
-            for (int k = 2; k < 6; k++) a[k] = red[w][k] > a[k] ? red[w][k] : a[k];
-        }
-        if (a[0]) atomicOr(&words[0], kErrIndex);
-        if (a[1]) atomicAdd(&words[1], a[1]);
-        for (int k = 2; k < 6; k++)
-            if (a[k]) atomicMax(&words[k], a[k]);
-    }
+    locate_reduce(werr, wodd, hx, lx, hy, ly, kErrIndex, words);
 }
 
 // ---- 2. keys -------------------------------------------------------------------------------------
@@ -451,28 +407,6 @@ __global__ void __launch_bounds__(kTB) tagg_fix(const RunPart* carry, const Cell
 }
 
 // ---- host side -----------------------------------------------------------------------------------------
-#define GCHK(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kTB - 1) / kTB); }
-
-template <typename T>
-int scratch(geohip_ctx* ctx, GSlot slot, size_t bytes, T** out) {
-    void* p = nullptr;
-    const int rc = ctx_ensure(ctx, slot, bytes, &p);
-    *out = static_cast<T*>(p);
-    return rc;
-}
-
-unsigned bits_for(unsigned span) {  // bits that hold 0 .. span - 1
-    unsigned b = 0;
-    while (b < 32 && (1ull << b) < span) b++;
-    return b;
-}
-
 struct TaggIn {
     const unsigned* traj_of;
     const unsigned* perm;
@@ -488,11 +422,11 @@ int tagg_sorted(geohip_ctx* ctx, const TaggIn& in, const int2* cxy, const TaggOu
     hipStream_t st = ctx_stream(ctx);
     const unsigned ns = in.n_sel, nchunks = (ns + kChunk - 1) / kChunk;
     size_t sort_tb = 0, run_tb = 0, cell_tb = 0;
-    GCHK(rocprim::radix_sort_pairs(nullptr, sort_tb, (const K*)nullptr, (K*)nullptr, (const unsigned*)nullptr,
-                                   (unsigned*)nullptr, ns, 0, in.bits ? in.bits : 1, st));
-    GCHK(rocprim::exclusive_scan(nullptr, run_tb, (RunPart*)nullptr, (RunPart*)nullptr, RunPart{}, (size_t)nchunks + 1,
-                                 RunPartOp(), st));
-    GCHK(rocprim::exclusive_scan(nullptr, cell_tb, (CellV*)nullptr, (CellV*)nullptr, CellV{}, (size_t)nchunks, CellPartOp(), st));
+    GEOHIP_CHK(rocprim::radix_sort_pairs(nullptr, sort_tb, (const K*)nullptr, (K*)nullptr, (const unsigned*)nullptr,
+                                         (unsigned*)nullptr, ns, 0, in.bits ? in.bits : 1, st));
+    GEOHIP_CHK(rocprim::exclusive_scan(nullptr, run_tb, (RunPart*)nullptr, (RunPart*)nullptr, RunPart{}, (size_t)nchunks + 1,
+                                       RunPartOp(), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(nullptr, cell_tb, (CellV*)nullptr, (CellV*)nullptr, CellV{}, (size_t)nchunks, CellPartOp(), st));
     size_t temp_bytes = sort_tb > run_tb ? sort_tb : run_tb;
     temp_bytes = (temp_bytes > cell_tb ? temp_bytes : cell_tb) + 16;
     K *key, *key2;
@@ -501,17 +435,17 @@ int tagg_sorted(geohip_ctx* ctx, const TaggIn& in, const int2* cxy, const TaggOu
     void* temp;
     RunPart *rp, *rpx;
     CellV *cp, *cpx, *open;
-    int rc = scratch(ctx, G_KEY, (size_t)ns * sizeof(K), &key);
-    if (!rc) rc = scratch(ctx, G_KEY2, (size_t)ns * sizeof(K), &key2);
-    if (!rc) rc = scratch(ctx, G_VAL2, (size_t)ns * 4, &val2);
-    if (!rc) rc = scratch(ctx, G_TS, (size_t)ns * 8, &ts_s);
-    if (!rc) rc = scratch(ctx, G_TR, (size_t)ns * 4, &tr_s);
-    if (!rc) rc = scratch(ctx, G_TEMP, temp_bytes, &temp);
+    int rc = scratch<G_KEY>(ctx, (size_t)ns * sizeof(K), &key);
+    if (!rc) rc = scratch<G_KEY2>(ctx, (size_t)ns * sizeof(K), &key2);
+    if (!rc) rc = scratch<G_VAL2>(ctx, (size_t)ns * 4, &val2);
+    if (!rc) rc = scratch<G_TS>(ctx, (size_t)ns * 8, &ts_s);
+    if (!rc) rc = scratch<G_TR>(ctx, (size_t)ns * 4, &tr_s);
+    if (!rc) rc = scratch<G_TEMP>(ctx, temp_bytes, &temp);
     // rp | rpx (nchunks + 1 RunPart each, 32 B) | cp | cpx | open (nchunks CellV each, 40 B): 8-byte aligned throughout
     static_assert(sizeof(RunPart) % 8 == 0 && sizeof(CellV) % 8 == 0, "packed back to back");
     char* parts;
     const size_t rp_bytes = ((size_t)nchunks + 1) * sizeof(RunPart), cp_bytes = (size_t)nchunks * sizeof(CellV);
-    if (!rc) rc = scratch(ctx, G_PARTS, 2 * rp_bytes + 3 * cp_bytes, &parts);
+    if (!rc) rc = scratch<G_PARTS>(ctx, 2 * rp_bytes + 3 * cp_bytes, &parts);
     if (rc) return rc;
     rp = reinterpret_cast<RunPart*>(parts);
     rpx = reinterpret_cast<RunPart*>(parts + rp_bytes);
@@ -523,21 +457,21 @@ int tagg_sorted(geohip_ctx* ctx, const TaggIn& in, const int2* cxy, const TaggOu
     const unsigned* sval = in.perm;
     if (in.bits) {  // one cell: perm is in (cell, trajectory, index) order as it stands
         size_t tb = temp_bytes;
-        GCHK(rocprim::radix_sort_pairs(temp, tb, (const K*)key, key2, in.perm, val2, ns, 0, in.bits, st));
+        GEOHIP_CHK(rocprim::radix_sort_pairs(temp, tb, (const K*)key, key2, in.perm, val2, ns, 0, in.bits, st));
         skey = key2;
         sval = val2;
     }
     tlaunch(ctx, tagg_partials<K>, dim3(nchunks), dim3(kTB), 0, st, skey, sval, in.traj_of, in.ts, ns, nchunks, ts_s, tr_s, rp);
     size_t tb = temp_bytes;
-    GCHK(rocprim::exclusive_scan(temp, tb, rp, rpx, RunPart{RunV::identity(), 0u, 0u, 0u, 0u}, (size_t)nchunks + 1, RunPartOp(), st));
-    GCHK(hipMemsetAsync(open, 0, (size_t)nchunks * sizeof(CellV), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(temp, tb, rp, rpx, RunPart{RunV::identity(), 0u, 0u, 0u, 0u}, (size_t)nchunks + 1, RunPartOp(), st));
+    GEOHIP_CHK(hipMemsetAsync(open, 0, (size_t)nchunks * sizeof(CellV), st));
     tlaunch(ctx, tagg_apply<K>, dim3(nchunks), dim3(kTB), 0, st, skey, sval, (const long long*)ts_s, (const unsigned*)tr_s, ns,
             (const RunPart*)rpx, in.cx0, in.cy0, in.by, out, cp, open);
     tb = temp_bytes;
-    GCHK(rocprim::exclusive_scan(temp, tb, cp, cpx, CellV::identity(), (size_t)nchunks, CellPartOp(), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(temp, tb, cp, cpx, CellV::identity(), (size_t)nchunks, CellPartOp(), st));
     tlaunch(ctx, tagg_fix, dim3(blocks_for((uint64_t)nchunks + 1)), dim3(kTB), 0, st, (const RunPart*)rpx, (const CellV*)cpx,
             (const CellV*)open, nchunks, out, words);
-    GCHK(hipGetLastError());
+    GEOHIP_CHK(hipGetLastError());
     return GEOHIP_OK;
 }
 
@@ -568,7 +502,7 @@ int geohip_tagg_cells(geohip_ctx* ctx, const geohip_grid* grid, const double* x,
         return ctx_fail(ctx, GEOHIP_ERR_ARG, "visit_off, visit_traj and visit_len are null together");
     hipStream_t st = ctx_stream(ctx);
     if (n_sel == 0) {
-        if (visits) GCHK(hipMemsetAsync(visit_off, 0, 4, st));
+        if (visits) GEOHIP_CHK(hipMemsetAsync(visit_off, 0, 4, st));
         return GEOHIP_OK;
     }
     if (!x || !y || !ts || !traj_of || !perm || !cell_xy || !cell_count || !cell_sum || !cell_avg || !cell_min ||
@@ -577,18 +511,17 @@ int geohip_tagg_cells(geohip_ctx* ctx, const geohip_grid* grid, const double* x,
     const unsigned ns = (unsigned)n_sel;
     int2* cxy;
     unsigned* words;
-    rc = scratch(ctx, G_CXY, (size_t)ns * sizeof(int2), &cxy);
-    if (!rc) rc = scratch(ctx, G_WORDS, 64, &words);
+    rc = scratch<G_CXY>(ctx, (size_t)ns * sizeof(int2), &cxy);
+    if (!rc) rc = scratch<G_WORDS>(ctx, 64, &words);
     if (rc) return rc;
-    GCHK(hipMemsetAsync(words, 0, 64, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, 64, st));
     tlaunch(ctx, tagg_locate, dim3(blocks_for(ns)), dim3(kTB), 0, st, x, y, (unsigned)n, traj_of, (unsigned)n_traj, perm, ns,
             grid->min_x, grid->min_y, grid->cell_len, cxy, words);
-    GCHK(hipGetLastError());
-    uint64_t* pin = ctx_pinned(ctx);
-    GCHK(hipMemcpyAsync(pin, words, 24, hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
-    const unsigned err = (unsigned)(pin[0] & 0xffffffffu), odd = (unsigned)(pin[0] >> 32);
-    if (err & kErrIndex) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_tagg_cells: perm entry >= n, or traj_of[perm[j]] >= n_traj");
+    WordsHead head;  // the error bits, the points outside [kCellLo, kCellHi], the rectangle as four maxima
+    rc = read_words_head(ctx, words, st, &head);
+    if (rc) return rc;
+    const unsigned odd = head.count;
+    if (head.err & kErrIndex) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_tagg_cells: perm entry >= n, or traj_of[perm[j]] >= n_traj");
     if (odd) {
         *n_odd = odd;
         return ctx_fail(ctx, GEOHIP_ERR_ARG,
@@ -599,9 +532,9 @@ int geohip_tagg_cells(geohip_ctx* ctx, const geohip_grid* grid, const double* x,
     in.perm = perm;
     in.ts = reinterpret_cast<const long long*>(ts);
     in.n_sel = ns;
-    const int cx1 = kCellLo + (int)(pin[1] & 0xffffffffu), cy1 = kCellLo + (int)(pin[2] & 0xffffffffu);
-    in.cx0 = kCellHi - (int)(pin[1] >> 32);
-    in.cy0 = kCellHi - (int)(pin[2] >> 32);
+    const int cx1 = kCellLo + (int)head.hx, cy1 = kCellLo + (int)head.hy;
+    in.cx0 = kCellHi - (int)head.lx;
+    in.cy0 = kCellHi - (int)head.ly;
     const unsigned bx = bits_for((unsigned)(cx1 - in.cx0 + 1));
     in.by = bits_for((unsigned)(cy1 - in.cy0 + 1));
     in.bits = bx + in.by;
@@ -619,8 +552,9 @@ int geohip_tagg_cells(geohip_ctx* ctx, const geohip_grid* grid, const double* x,
     out.visit_len = reinterpret_cast<long long*>(visit_len);
     rc = in.bits <= 32 ? tagg_sorted<uint32_t>(ctx, in, cxy, out, words) : tagg_sorted<uint64_t>(ctx, in, cxy, out, words);
     if (rc) return rc;
-    GCHK(hipMemcpyAsync(pin, words + 6, 8, hipMemcpyDeviceToHost, st));
-    GCHK(hipStreamSynchronize(st));
+    uint64_t* pin = ctx_pinned(ctx);
+    GEOHIP_CHK(hipMemcpyAsync(pin, words + 6, 8, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     *n_cells = pin[0] & 0xffffffffu;
     *n_visits = pin[0] >> 32;
     return GEOHIP_OK;

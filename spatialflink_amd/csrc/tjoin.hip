@@ -20,7 +20,7 @@
 //                  points that take part (selected, trajectory of >= min_points points, cell inside the
 //                  grid) and their cell rectangle (one set of atomics per workgroup);
 //   2. tj_qrect    per query point its cell square clipped to the grid, with the reference's error
-//                  cases (the restatement of jq_rect, cell_kernels.hip);
+//                  cases (d_neighbor_square, locate.h: the one jq_rect of cell_kernels.hip calls);
 //      -- read-back: errors, the count, the rectangle --
 //   3. tj_keys     key = (cx - cx0) * H + (cy - cy0) inside the rectangle, W * H for a point that
 //                  takes no part; rocPRIM stable LSD radix sort of (key, index) over bits(W * H + 1);
@@ -43,7 +43,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cmath>
 #include <string>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -51,16 +50,11 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "geohip.h"
-#include "join.h"
-#include "locate.h"
+#include "traj_common.h"
 
 namespace geohip {
 namespace {
 
-constexpr int kTB = 256;
-constexpr int kWaves = kTB / 64;
-constexpr uint64_t kMaxPoints = 1ull << 30;
-constexpr unsigned kNone = 0xffffffffu;
 constexpr unsigned long long kEmpty = ~0ull;  // no key: ta < 2^30, so a key's top bit is clear
 // cell starts are built while the occupied rectangle holds fewer cells (64 MiB of offsets)
 constexpr uint64_t kTJoinCellBudget = 1ull << 24;
@@ -71,10 +65,8 @@ constexpr uint64_t kTableFirst = 1ull << 22;
 constexpr uint64_t kTableMax = 1ull << 30;
 constexpr unsigned kMaxProbe = 1u << 14;  // a probe chain this long abandons the pass (the table grows)
 
-// scratch slots (ctx_ensure; the call owns them for its own duration on the ctx stream).  Only
-// slots 0..9, as traj.hip and tagg.hip: they carry nothing from one call to the next.
+// scratch slots (kCallSlots, traj_common.h)
 enum TSlot { T_WORDS, T_KEY, T_KEY2, T_REC, T_CELL, T_RECT, T_TEMP, T_TABLE, T_OUT };
-static_assert(T_OUT <= 9, "scratch slots that no call keeps state in");
 
 // words block (16 u32): [0] error bits, [1] ordinary points that take part, [2..5] their cell
 // rectangle as maxima of cx, n - 1 - cx, cy, n - 1 - cy, [6] keys inserted by the probe pass,
@@ -91,25 +83,12 @@ struct TjRec {
 };
 static_assert(sizeof(TjRec) == 24, "24-byte records");
 
-struct QRect {
-    int32_t x0, x1, y0, y1;  // cells, clipped; x0 > x1 = empty
-};
-
 struct TjGeom {
     double mnx, mny, l;
     int32_t n, lc;   // cells per side, candidate layers
     int all_cells;   // r == 0: every cell (UniformGrid.java:264-266)
     unsigned min_points;
 };
-
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // Whether ordinary point i takes part, and its cell: selected, its trajectory a trajectory under
 // min_points, its unclipped cell a cell of the grid (the key of any other cell equals no
@@ -132,7 +111,6 @@ __device__ __forceinline__ bool a_point(const double* x, const double* y, const 
 // ---- 1. ordinary points: checks, count, rectangle ---------------------------------------------
 __global__ void __launch_bounds__(kTB) tj_locate(const double* x, const double* y, unsigned n, const unsigned* traj_of,
                                                  const unsigned* traj_off, unsigned nt, TjGeom g, unsigned* words) {
-    __shared__ unsigned red[kWaves][6];
     unsigned hx = 0, lx = 0, hy = 0, ly = 0, cnt = 0;
     bool err = false;
     // a grid-stride loop: the atomics below all go to one line, so their number is the grid's, not n / 256
@@ -148,88 +126,15 @@ __global__ void __launch_bounds__(kTB) tj_locate(const double* x, const double* 
         }
         err = err || e;
     }
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const unsigned werr = __ballot(err) ? 1u : 0u;
-    unsigned win = cnt;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) win += __shfl_xor(win, d);
-    hx = wave_max(hx);
-    lx = wave_max(lx);
-    hy = wave_max(hy);
-    ly = wave_max(ly);
-    if (lane == 0) {
-        red[wave][0] = werr;
-        red[wave][1] = win;
-        red[wave][2] = hx;
-        red[wave][3] = lx;
-        red[wave][4] = hy;
-        red[wave][5] = ly;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned a[6] = {0, 0, 0, 0, 0, 0};
-        for (int w = 0; w < kWaves; w++) {
-            a[0] |= red[w][0];
-            a[1] += red[w][1];
-            for (int k = 2; k < 6; k++) a[k] = red[w][k] > a[k] ? red[w][k] : a[k];
-        }
-        if (a[0]) atomicOr(&words[0], kErrTrajA);
-        if (a[1]) atomicAdd(&words[1], a[1]);
-        for (int k = 2; k < 6; k++)
-            if (a[k]) atomicMax(&words[k], a[k]);
-    }
+    locate_reduce(werr, wave_sum(cnt), hx, lx, hy, ly, kErrTrajA, words);
 }
 
 // ---- 2. query squares ------------------------------------------------------------------------------
-// String.format("%05d", v) and Integer.parseInt(s.replaceFirst("^0+(?!$)", "")) as jq_rect has them
-// (HelperClass.java:54-63): a query cell outside [-9999, 99999] makes a key that is not 10 characters,
-// which getIntCellIndices splits after the fifth.
-__device__ __forceinline__ int d_format05(int32_t v, char* out) {
-    char digits[12];
-    int nd = 0;
-    int64_t a = v;
-    const bool neg = a < 0;
-    if (neg) a = -a;
-    do {
-        digits[nd++] = (char)('0' + (int)(a % 10));
-        a /= 10;
-    } while (a != 0);
-    const int width = nd + (neg ? 1 : 0);
-    int p = 0;
-    if (neg) out[p++] = '-';
-    for (int i = width; i < 5; i++) out[p++] = '0';
-    while (nd > 0) out[p++] = digits[--nd];
-    return p;
-}
-__device__ __forceinline__ bool d_java_parse(const char* s, int len, int32_t* out) {
-    int skip = 0;
-    while (skip < len - 1 && s[skip] == '0') skip++;
-    s += skip;
-    len -= skip;
-    if (len <= 0) return false;
-    bool neg = false;
-    int p = 0;
-    if (s[0] == '+' || s[0] == '-') {
-        if (len == 1) return false;
-        neg = s[0] == '-';
-        p = 1;
-    }
-    int64_t v = 0;
-    for (; p < len; p++) {
-        if (s[p] < '0' || s[p] > '9') return false;
-        v = v * 10 + (s[p] - '0');
-        if (v > 2147483648LL) return false;
-    }
-    if (neg) v = -v;
-    if (v > INT32_MAX || v < INT32_MIN) return false;
-    *out = (int32_t)v;
-    return true;
-}
-
-// UniformGrid.getNeighboringCells (UniformGrid.java:261-293) of every selected query point: the
-// valid cells of the int-wrapping square [c - lc, c + lc] around the point's unclipped cell.  The
-// reference replicates a point before it knows the point's trajectory, so the error cases count
-// for one-point trajectories too; an unselected point takes no part at all.
+// UniformGrid.getNeighboringCells (UniformGrid.java:261-293) of every selected query point
+// (d_neighbor_square, locate.h).  The reference replicates a point before it knows the point's
+// trajectory, so the error cases count for one-point trajectories too; an unselected point takes no
+// part at all.
 __global__ void __launch_bounds__(kTB) tj_qrect(const double* qx, const double* qy, unsigned nq, const unsigned* traj_of,
                                                 const unsigned* traj_off, unsigned nt, TjGeom g, QRect* rect, unsigned* words) {
     const unsigned i = blockIdx.x * kTB + threadIdx.x;
@@ -247,32 +152,8 @@ __global__ void __launch_bounds__(kTB) tj_qrect(const double* qx, const double* 
     }
     QRect R{0, g.n - 1, 0, g.n - 1};
     if (!g.all_cells) {
-        const int32_t cx = d_axis_cell(qx[i], g.mnx, g.l), cy = d_axis_cell(qy[i], g.mny, g.l);
-        int32_t ci = cx, cj = cy;
-        bool ok = true;
-        if (!(cx >= -9999 && cx <= 99999 && cy >= -9999 && cy <= 99999)) {
-            char key[24];
-            int n = d_format05(cx, key);
-            n += d_format05(cy, key + n);
-            ok = d_java_parse(key, 5, &ci) && d_java_parse(key + 5, n - 5, &cj);
-        }
-        if (!ok) {
-            atomicOr(&words[0], kErrKey);
-            R = none;
-        } else {
-            const int32_t lo_i = (int32_t)(uint32_t)(uint64_t)((int64_t)ci - g.lc);
-            const int32_t hi_i = (int32_t)(uint32_t)(uint64_t)((int64_t)ci + g.lc);
-            const int32_t lo_j = (int32_t)(uint32_t)(uint64_t)((int64_t)cj - g.lc);
-            const int32_t hi_j = (int32_t)(uint32_t)(uint64_t)((int64_t)cj + g.lc);
-            if (lo_i > hi_i || lo_j > hi_j) {
-                R = none;
-            } else if (hi_i == INT32_MAX || hi_j == INT32_MAX) {
-                atomicOr(&words[0], kErrLoop);
-                R = none;
-            } else {
-                R = QRect{lo_i > 0 ? lo_i : 0, hi_i < g.n - 1 ? hi_i : g.n - 1, lo_j > 0 ? lo_j : 0, hi_j < g.n - 1 ? hi_j : g.n - 1};
-            }
-        }
+        const int st = d_neighbor_square(d_axis_cell(qx[i], g.mnx, g.l), d_axis_cell(qy[i], g.mny, g.l), g.lc, g.n, R);
+        if (st) atomicOr(&words[0], st == 1 ? kErrKey : kErrLoop);
     }
     if (traj_off[t + 1] - traj_off[t] < g.min_points) R = none;  // no trajectory: its hits are dropped
     rect[i] = R;
@@ -298,17 +179,6 @@ __global__ void __launch_bounds__(kTB) tj_records(const unsigned* sval, unsigned
     if (j >= nv) return;
     const unsigned i = sval[j];  // a point that takes part: tj_keys gave every other the last key
     rec[j] = TjRec{x[i], y[i], traj_of[i], 0u};
-}
-
-// first j in [0, n) with key[j] >= k (n where none)
-__device__ __forceinline__ unsigned lower_bound(const unsigned* key, unsigned n, unsigned k) {
-    unsigned lo = 0, hi = n;
-    while (lo < hi) {
-        const unsigned mid = lo + (hi - lo) / 2;
-        if (key[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // ---- 5. cell starts ----------------------------------------------------------------------------------
@@ -468,35 +338,6 @@ __global__ void __launch_bounds__(kTB) tj_write(const unsigned long long* key, u
     out[2 * (size_t)i + 1] = (unsigned)(k & ((1ull << kb) - 1));
 }
 
-// ---- host side -----------------------------------------------------------------------------------------
-#define JCHK(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kTB - 1) / kTB); }
-
-template <typename T>
-int scratch(geohip_ctx* ctx, TSlot slot, size_t bytes, T** out) {
-    void* p = nullptr;
-    const int rc = ctx_ensure(ctx, slot, bytes, &p);
-    *out = static_cast<T*>(p);
-    return rc;
-}
-
-unsigned bits_for(uint64_t span) {  // bits that hold 0 .. span - 1
-    unsigned b = 0;
-    while (b < 63 && (1ull << b) < span) b++;
-    return b;
-}
-
-uint64_t pow2_at_least(uint64_t v) {
-    uint64_t p = 2;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 }  // namespace
 }  // namespace geohip
 
@@ -513,11 +354,8 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
     if (!out_count) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null out_count");
     *out_count = 0;
     if (ctx_mem(ctx) != GEOHIP_MEM_DEVICE) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_tjoin_pp takes device memory");
-    if (!grid) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null grid");
-    if (!(grid->n > 0) || !(grid->cell_len > 0) || !std::isfinite(grid->cell_len) || !std::isfinite(grid->min_x) ||
-        !std::isfinite(grid->min_y))
-        return ctx_fail(ctx, GEOHIP_ERR_ARG, "invalid grid");
-    if (grid->n > 99999) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "more than 99999 cells per side");
+    rc = check_grid_basic(ctx, grid, "grid");
+    if (rc) return rc;
     if (na > kMaxPoints || nb > kMaxPoints || nta > kMaxPoints || ntb > kMaxPoints)
         return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "more than 2^30 points");
     if (cap && !out_tpairs) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null out_tpairs");
@@ -538,24 +376,23 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
     // rect (nb QRect, 16 B each) | width (nb + 1 u64) | item_off (nb + 1 u64)
     char* qblock;
     const size_t rect_bytes = (size_t)unb * sizeof(QRect), off_bytes = ((size_t)unb + 1) * 8;
-    rc = scratch(ctx, T_WORDS, kWordsBytes, &words);
-    if (!rc) rc = scratch(ctx, T_RECT, rect_bytes + 2 * off_bytes, &qblock);
+    rc = scratch<T_WORDS>(ctx, kWordsBytes, &words);
+    if (!rc) rc = scratch<T_RECT>(ctx, rect_bytes + 2 * off_bytes, &qblock);
     if (rc) return rc;
     rect = reinterpret_cast<QRect*>(qblock);
     unsigned long long* width = reinterpret_cast<unsigned long long*>(qblock + rect_bytes);
     unsigned long long* item_off = reinterpret_cast<unsigned long long*>(qblock + rect_bytes + off_bytes);
-    JCHK(hipMemsetAsync(words, 0, kWordsBytes, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, kWordsBytes, st));
     if (na) {
         const unsigned want = blocks_for(una), most = (unsigned)ctx_cus(ctx) * 8u;
         tlaunch(ctx, tj_locate, dim3(want < most ? want : most), dim3(kTB), 0, st, ax, ay, una, traj_of_a, traj_off_a,
                 (unsigned)nta, g, words);
     }
     tlaunch(ctx, tj_qrect, dim3(blocks_for(unb)), dim3(kTB), 0, st, bx, by, unb, traj_of_b, traj_off_b, (unsigned)ntb, g, rect, words);
-    JCHK(hipGetLastError());
-    uint64_t* pin = ctx_pinned(ctx);
-    JCHK(hipMemcpyAsync(pin, words, 24, hipMemcpyDeviceToHost, st));
-    JCHK(hipStreamSynchronize(st));
-    const unsigned err = (unsigned)(pin[0] & 0xffffffffu), nv = (unsigned)(pin[0] >> 32);
+    WordsHead head;  // the error bits, the points that take part, their rectangle as four maxima
+    rc = read_words_head(ctx, words, st, &head);
+    if (rc) return rc;
+    const unsigned err = head.err, nv = head.count;
     if (err & kErrTrajA) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_tjoin_pp: traj_of_a entry >= nta");
     if (err & kErrTrajB) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_tjoin_pp: traj_of_b entry >= ntb");
     if (err & kErrKey)
@@ -563,8 +400,8 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
     if (err & kErrLoop)
         return ctx_fail(ctx, GEOHIP_ERR_ARG, "query point neighbourhood reaches Integer.MAX_VALUE: the reference loop does not terminate");
     if (nv == 0) return GEOHIP_OK;
-    const int cx1 = (int)(pin[1] & 0xffffffffu), cx0 = grid->n - 1 - (int)(pin[1] >> 32);
-    const int cy1 = (int)(pin[2] & 0xffffffffu), cy0 = grid->n - 1 - (int)(pin[2] >> 32);
+    const int cx1 = (int)head.hx, cx0 = grid->n - 1 - (int)head.lx;
+    const int cy1 = (int)head.hy, cy0 = grid->n - 1 - (int)head.ly;
     const uint64_t W = (uint64_t)(cx1 - cx0 + 1), H = (uint64_t)(cy1 - cy0 + 1), ncells = W * H;
     if (ncells >= 0xffffffffull)
         return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "the occupied cell rectangle holds 2^32 - 1 cells or more");
@@ -577,30 +414,30 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
     TjRec* rec;
     void* temp;
     size_t sort_tb = 0, scan_tb = 0;
-    JCHK(rocprim::radix_sort_pairs(nullptr, sort_tb, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                   (unsigned*)nullptr, una, 0, key_bits, st));
-    JCHK(rocprim::exclusive_scan(nullptr, scan_tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull,
-                                 (size_t)unb + 1, rocprim::plus<unsigned long long>(), st));
+    GEOHIP_CHK(rocprim::radix_sort_pairs(nullptr, sort_tb, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
+                                         (unsigned*)nullptr, una, 0, key_bits, st));
+    GEOHIP_CHK(rocprim::exclusive_scan(nullptr, scan_tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull,
+                                       (size_t)unb + 1, rocprim::plus<unsigned long long>(), st));
     size_t temp_bytes = (sort_tb > scan_tb ? sort_tb : scan_tb) + 16;
-    rc = scratch(ctx, T_KEY, (size_t)una * 8, &key);  // key | val
-    if (!rc) rc = scratch(ctx, T_KEY2, (size_t)una * 8, &key2);
-    if (!rc) rc = scratch(ctx, T_REC, (size_t)nv * sizeof(TjRec), &rec);
-    if (!rc) rc = scratch(ctx, T_TEMP, temp_bytes, &temp);
-    if (!rc && csr) rc = scratch(ctx, T_CELL, (size_t)(ncells + 1) * 4, &cell_off);
+    rc = scratch<T_KEY>(ctx, (size_t)una * 8, &key);  // key | val
+    if (!rc) rc = scratch<T_KEY2>(ctx, (size_t)una * 8, &key2);
+    if (!rc) rc = scratch<T_REC>(ctx, (size_t)nv * sizeof(TjRec), &rec);
+    if (!rc) rc = scratch<T_TEMP>(ctx, temp_bytes, &temp);
+    if (!rc && csr) rc = scratch<T_CELL>(ctx, (size_t)(ncells + 1) * 4, &cell_off);
     if (rc) return rc;
     unsigned *val = key + una, *val2 = key2 + una;
     tlaunch(ctx, tj_keys, dim3(blocks_for(una)), dim3(kTB), 0, st, ax, ay, una, traj_of_a, traj_off_a, (unsigned)nta, g, cx0, cy0,
             (unsigned)H, (unsigned)ncells, key, val);
     size_t tb = temp_bytes;
-    JCHK(rocprim::radix_sort_pairs(temp, tb, (const unsigned*)key, key2, (const unsigned*)val, val2, una, 0, key_bits, st));
+    GEOHIP_CHK(rocprim::radix_sort_pairs(temp, tb, (const unsigned*)key, key2, (const unsigned*)val, val2, una, 0, key_bits, st));
     tlaunch(ctx, tj_records, dim3(blocks_for(nv)), dim3(kTB), 0, st, (const unsigned*)val2, nv, ax, ay, traj_of_a, rec);
     if (csr)
         tlaunch(ctx, tj_cells, dim3(blocks_for(ncells + 1)), dim3(kTB), 0, st, (const unsigned*)key2, nv, (unsigned)ncells, cell_off);
     // 6: the work items
     tlaunch(ctx, tj_qwidth, dim3(blocks_for((uint64_t)unb + 1)), dim3(kTB), 0, st, rect, unb, cx0, cx1, cy0, cy1, width);
     tb = temp_bytes;
-    JCHK(rocprim::exclusive_scan(temp, tb, width, item_off, 0ull, (size_t)unb + 1, rocprim::plus<unsigned long long>(), st));
-    JCHK(hipGetLastError());
+    GEOHIP_CHK(rocprim::exclusive_scan(temp, tb, width, item_off, 0ull, (size_t)unb + 1, rocprim::plus<unsigned long long>(), st));
+    GEOHIP_CHK(hipGetLastError());
 
     // 7: probe into the hash set, growing it until a pass ends at or below half load
     const unsigned kb = bits_for(ntb), ka = bits_for(nta);
@@ -618,12 +455,13 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
     const unsigned probe_blocks = (unsigned)ctx_cus(ctx) * (unsigned)(resident < 8 ? resident : 8);
     uint64_t count = 0;
     unsigned long long* table = nullptr;
+    uint64_t* pin = ctx_pinned(ctx);
     for (;;) {
         if (slots > kTableMax) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "more than 2^29 distinct trajectory pairs");
-        rc = scratch(ctx, T_TABLE, (size_t)slots * 8, &table);
+        rc = scratch<T_TABLE>(ctx, (size_t)slots * 8, &table);
         if (rc) return rc;
-        JCHK(hipMemsetAsync(table, 0xff, (size_t)slots * 8, st));
-        JCHK(hipMemsetAsync(words + 6, 0, 8, st));
+        GEOHIP_CHK(hipMemsetAsync(table, 0xff, (size_t)slots * 8, st));
+        GEOHIP_CHK(hipMemsetAsync(words + 6, 0, 8, st));
         TjProbe p;
         p.rec = rec;
         p.skey = key2;
@@ -647,9 +485,9 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
         p.slot_mask = (unsigned)(slots - 1);
         p.words = words;
         tlaunch(ctx, tj_probe, dim3(probe_blocks), dim3(kTB), 0, st, p);
-        JCHK(hipGetLastError());
-        JCHK(hipMemcpyAsync(pin, words + 6, 8, hipMemcpyDeviceToHost, st));
-        JCHK(hipStreamSynchronize(st));
+        GEOHIP_CHK(hipGetLastError());
+        GEOHIP_CHK(hipMemcpyAsync(pin, words + 6, 8, hipMemcpyDeviceToHost, st));
+        GEOHIP_CHK(hipStreamSynchronize(st));
         ctx_tjoin_debug(ctx)[3]++;  // probe passes (scripts/tjoin_time.py reads it through the hook)
         count = pin[0] & 0xffffffffu;
         const bool gave_up = (pin[0] >> 32) != 0;
@@ -664,24 +502,24 @@ int geohip_tjoin_pp(geohip_ctx* ctx, const geohip_grid* grid, const double* ax, 
     const unsigned m = (unsigned)count;
     unsigned long long* okey;
     size_t sel_tb = 0, ksort_tb = 0;
-    JCHK(rocprim::select(nullptr, sel_tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
-                         (size_t)slots, IsKey(), st));
-    JCHK(rocprim::radix_sort_keys(nullptr, ksort_tb, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, m, 0,
-                                  ka + kb ? ka + kb : 1, st));
+    GEOHIP_CHK(rocprim::select(nullptr, sel_tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
+                               (size_t)slots, IsKey(), st));
+    GEOHIP_CHK(rocprim::radix_sort_keys(nullptr, ksort_tb, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, m, 0,
+                                        ka + kb ? ka + kb : 1, st));
     temp_bytes = (sel_tb > ksort_tb ? sel_tb : ksort_tb) + 16;
-    rc = scratch(ctx, T_OUT, (size_t)m * 16, &okey);
-    if (!rc) rc = scratch(ctx, T_TEMP, temp_bytes, &temp);
+    rc = scratch<T_OUT>(ctx, (size_t)m * 16, &okey);
+    if (!rc) rc = scratch<T_TEMP>(ctx, temp_bytes, &temp);
     if (rc) return rc;
     tb = temp_bytes;
-    JCHK(rocprim::select(temp, tb, table, okey, words + 8, (size_t)slots, IsKey(), st));
+    GEOHIP_CHK(rocprim::select(temp, tb, table, okey, words + 8, (size_t)slots, IsKey(), st));
     const unsigned long long* sorted = okey;
     if (ka + kb) {
         tb = temp_bytes;
-        JCHK(rocprim::radix_sort_keys(temp, tb, (const unsigned long long*)okey, okey + m, m, 0, ka + kb, st));
+        GEOHIP_CHK(rocprim::radix_sort_keys(temp, tb, (const unsigned long long*)okey, okey + m, m, 0, ka + kb, st));
         sorted = okey + m;
     }
     tlaunch(ctx, tj_write, dim3(blocks_for(m)), dim3(kTB), 0, st, sorted, m, kb, out_tpairs);
-    JCHK(hipGetLastError());
+    GEOHIP_CHK(hipGetLastError());
     return GEOHIP_OK;
 }
 

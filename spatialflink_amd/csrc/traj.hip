@@ -1,7 +1,7 @@
 // traj.hip -- the trajectory family's keyBy(objID) on the device, and the two operators it fully
 // determines: windowed PointTStatsQuery and windowed / real-time PointTFilterQuery.
 //
-// Reference (paths relative to /root/reference/src/main/java/GeoFlink):
+// Reference (paths relative to the reference's src/main/java/GeoFlink):
 //   selection   spatialOperators/tStats/PointTStatsQuery.java:76-84, tFilter/PointTFilterQuery.java:62-73, 89-97:
 //               an empty trajIDSet selects every point, otherwise trajIDSet.contains(point.objID)
 //               (String.equals = byte equality of the UTF-8 stored here); a null objID is in no set;
@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -45,17 +46,14 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "geohip.h"
-#include "join.h"
+#include "traj_common.h"
 
 namespace geohip {
 namespace {
 
-constexpr unsigned kNone = 0xffffffffu;
 constexpr unsigned long long kOffMask = ~(1ull << 63);
-constexpr int kTB = 256;
-constexpr uint64_t kMaxPoints = 1ull << 30;  // table slots (<= 2^31) and indices stay below 0xffffffff
 
-// traj scratch slots (ctx_ensure; every call owns them for its own duration on the ctx stream)
+// scratch slots (kCallSlots, traj_common.h)
 enum TSlot { T_TAB, T_KEY, T_RANK, T_KEY2, T_VAL, T_VAL2, T_TEMP, T_WORDS, T_SETTAB, T_LIST };
 
 // words block: [0] error bits, [1] selected points, [2] queued long trajectories, [3] the null
@@ -433,27 +431,11 @@ __global__ void __launch_bounds__(kTB) traj_gather(const double* x, const double
 }
 
 // ---- host side --------------------------------------------------------------------------------
-#define TCHK(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kTB - 1) / kTB); }
-
 // slots - 1 of a table for n strings: a power of two >= max(2n, 64)
 unsigned table_mask(uint64_t n) {
     uint64_t m = 64;
     while (m < 2 * n) m <<= 1;
     return (unsigned)(m - 1);
-}
-
-template <typename T>
-int scratch(geohip_ctx* ctx, TSlot slot, size_t bytes, T** out) {
-    void* p = nullptr;
-    const int rc = ctx_ensure(ctx, slot, bytes, &p);
-    *out = static_cast<T*>(p);
-    return rc;
 }
 
 int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oid_off, uint64_t n,
@@ -472,36 +454,36 @@ int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oi
         return ctx_fail(ctx, GEOHIP_ERR_ARG, "null argument");
     hipStream_t st = ctx_stream(ctx);
     if (n == 0) {
-        TCHK(hipMemsetAsync(traj_off, 0, 4, st));
+        GEOHIP_CHK(hipMemsetAsync(traj_off, 0, 4, st));
         return GEOHIP_OK;
     }
     const unsigned nn = (unsigned)n, ss = (unsigned)s;
     const unsigned mask = table_mask(n), set_mask = table_mask(s);
     size_t scan_tb = 0, sort_tb = 0;
-    TCHK(rocprim::exclusive_scan(nullptr, scan_tb, (unsigned*)nullptr, (unsigned*)nullptr, 0u, n + 1,
-                                 rocprim::plus<unsigned>(), st));
-    TCHK(rocprim::radix_sort_pairs(nullptr, sort_tb, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
-                                   (unsigned*)nullptr, n, 0, 32, st));
+    GEOHIP_CHK(rocprim::exclusive_scan(nullptr, scan_tb, (unsigned*)nullptr, (unsigned*)nullptr, 0u, n + 1,
+                                       rocprim::plus<unsigned>(), st));
+    GEOHIP_CHK(rocprim::radix_sort_pairs(nullptr, sort_tb, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr,
+                                         (unsigned*)nullptr, n, 0, 32, st));
     const size_t temp_bytes = (scan_tb > sort_tb ? scan_tb : sort_tb) + 16;
     unsigned *tab, *key, *rank, *key2, *val, *val2, *words, *set_tab;
     void* temp;
-    rc = scratch(ctx, T_TAB, ((size_t)mask + 1) * 4, &tab);
-    if (!rc) rc = scratch(ctx, T_KEY, (n + 1) * 4, &key);
-    if (!rc) rc = scratch(ctx, T_RANK, (n + 1) * 4, &rank);
-    if (!rc) rc = scratch(ctx, T_KEY2, n * 4, &key2);
-    if (!rc) rc = scratch(ctx, T_VAL, n * 4, &val);
-    if (!rc) rc = scratch(ctx, T_VAL2, n * 4, &val2);
-    if (!rc) rc = scratch(ctx, T_TEMP, temp_bytes, &temp);
-    if (!rc) rc = scratch(ctx, T_WORDS, 64, &words);
-    if (!rc) rc = scratch(ctx, T_SETTAB, ((size_t)set_mask + 1) * 4, &set_tab);
+    rc = scratch<T_TAB>(ctx, ((size_t)mask + 1) * 4, &tab);
+    if (!rc) rc = scratch<T_KEY>(ctx, (n + 1) * 4, &key);
+    if (!rc) rc = scratch<T_RANK>(ctx, (n + 1) * 4, &rank);
+    if (!rc) rc = scratch<T_KEY2>(ctx, n * 4, &key2);
+    if (!rc) rc = scratch<T_VAL>(ctx, n * 4, &val);
+    if (!rc) rc = scratch<T_VAL2>(ctx, n * 4, &val2);
+    if (!rc) rc = scratch<T_TEMP>(ctx, temp_bytes, &temp);
+    if (!rc) rc = scratch<T_WORDS>(ctx, 64, &words);
+    if (!rc) rc = scratch<T_SETTAB>(ctx, ((size_t)set_mask + 1) * 4, &set_tab);
     if (rc) return rc;
     const Strs oid{oid_text, reinterpret_cast<const unsigned long long*>(oid_off)};
     const Strs set{set_text, reinterpret_cast<const unsigned long long*>(set_off)};
-    TCHK(hipMemsetAsync(tab, 0xff, ((size_t)mask + 1) * 4, st));
-    TCHK(hipMemsetAsync(words, 0, 64, st));
-    TCHK(hipMemsetAsync(words + 3, 0xff, 4, st));
+    GEOHIP_CHK(hipMemsetAsync(tab, 0xff, ((size_t)mask + 1) * 4, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, 64, st));
+    GEOHIP_CHK(hipMemsetAsync(words + 3, 0xff, 4, st));
     if (ss) {
-        TCHK(hipMemsetAsync(set_tab, 0xff, ((size_t)set_mask + 1) * 4, st));
+        GEOHIP_CHK(hipMemsetAsync(set_tab, 0xff, ((size_t)set_mask + 1) * 4, st));
         tlaunch(ctx, traj_set_build, dim3(blocks_for(s)), dim3(kTB), 0, st, set, ss, set_tab, set_mask, hmask, words);
     }
     tlaunch(ctx, traj_insert, dim3(blocks_for(n)), dim3(kTB), 0, st, oid, nn, set, ss, set_tab, set_mask, tab, mask, hmask,
@@ -509,11 +491,11 @@ int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oi
     unsigned* flag = key;  // dead once scanned
     tlaunch(ctx, traj_flag, dim3(blocks_for(n + 1)), dim3(kTB), 0, st, traj_of, tab, (const unsigned*)words, nn, flag);
     size_t tb = temp_bytes;
-    TCHK(rocprim::exclusive_scan(temp, tb, flag, rank, 0u, n + 1, rocprim::plus<unsigned>(), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(temp, tb, flag, rank, 0u, n + 1, rocprim::plus<unsigned>(), st));
     uint64_t* pin = ctx_pinned(ctx);
-    TCHK(hipMemcpyAsync(pin, words, 8, hipMemcpyDeviceToHost, st));
-    TCHK(hipMemcpyAsync(pin + 1, rank + n, 4, hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipMemcpyAsync(pin, words, 8, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipMemcpyAsync(pin + 1, rank + n, 4, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     const unsigned err = (unsigned)(pin[0] & 0xffffffffu);
     const unsigned nsel = (unsigned)(pin[0] >> 32), T = (unsigned)(pin[1] & 0xffffffffu);
     if (err & kErrOffsets) return ctx_fail(ctx, GEOHIP_ERR_ARG, "oid_off / set_off is not ascending (or names bytes of a null text)");
@@ -526,23 +508,22 @@ int traj_group_impl(geohip_ctx* ctx, const uint8_t* oid_text, const uint64_t* oi
     if (T && !traj_first) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null traj_first");
     tlaunch(ctx, traj_finalize, dim3(blocks_for(n)), dim3(kTB), 0, st, traj_of, tab, (const unsigned*)words, rank, nn, T, traj_first,
             key, val);
-    unsigned bits = 1;
-    while (bits < 32 && (1ull << bits) <= T) bits++;  // keys 0..T
+    const unsigned bits = std::max(1u, bits_for((uint64_t)T + 1));  // keys 0..T
     unsigned* sorted = nsel == nn ? perm : val2;
     tb = temp_bytes;
-    TCHK(rocprim::radix_sort_pairs(temp, tb, (const unsigned*)key, key2, (const unsigned*)val, sorted, n, 0, bits, st));
-    if (sorted != perm && nsel) TCHK(hipMemcpyAsync(perm, sorted, (size_t)nsel * 4, hipMemcpyDeviceToDevice, st));
+    GEOHIP_CHK(rocprim::radix_sort_pairs(temp, tb, (const unsigned*)key, key2, (const unsigned*)val, sorted, n, 0, bits, st));
+    if (sorted != perm && nsel) GEOHIP_CHK(hipMemcpyAsync(perm, sorted, (size_t)nsel * 4, hipMemcpyDeviceToDevice, st));
     tlaunch(ctx, traj_offsets, dim3(blocks_for((uint64_t)nsel + 1)), dim3(kTB), 0, st, key2, nsel, T, traj_off);
-    TCHK(hipGetLastError());
+    GEOHIP_CHK(hipGetLastError());
     return GEOHIP_OK;
 }
 
 // the words block's error bits after the queued work (geohip_tstats, geohip_traj_gather)
 int index_check(geohip_ctx* ctx, unsigned* words, hipStream_t st, const char* what) {
     uint64_t* pin = ctx_pinned(ctx);
-    TCHK(hipGetLastError());
-    TCHK(hipMemcpyAsync(pin, words, 8, hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipGetLastError());
+    GEOHIP_CHK(hipMemcpyAsync(pin, words, 8, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     if (pin[0] & kErrIndex) return ctx_fail(ctx, GEOHIP_ERR_ARG, std::string(what) + ": perm entry >= n, or traj_off not ascending or past n_sel");
     return GEOHIP_OK;
 }
@@ -593,10 +574,10 @@ int geohip_tstats(geohip_ctx* ctx, const double* x, const double* y, const int64
     hipStream_t st = ctx_stream(ctx);
     const unsigned T = (unsigned)n_traj;
     unsigned *words, *list;
-    rc = scratch(ctx, T_WORDS, 64, &words);
-    if (!rc) rc = scratch(ctx, T_LIST, (size_t)T * 4, &list);
+    rc = scratch<T_WORDS>(ctx, 64, &words);
+    if (!rc) rc = scratch<T_LIST>(ctx, (size_t)T * 4, &list);
     if (rc) return rc;
-    TCHK(hipMemsetAsync(words, 0, 64, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, 64, st));
     const long long* lts = reinterpret_cast<const long long*>(ts);
     long long* lot = reinterpret_cast<long long*>(out_temporal);
     tlaunch(ctx, tstats_serial, dim3(blocks_for(T)), dim3(kTB), 0, st, x, y, lts, (unsigned)n, perm, (unsigned)n_sel, traj_off,
@@ -619,9 +600,9 @@ int geohip_traj_gather(geohip_ctx* ctx, const double* x, const double* y, const 
     if (!x || !y || !perm || !out_x || !out_y || (ts && !out_ts)) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null argument");
     hipStream_t st = ctx_stream(ctx);
     unsigned* words;
-    rc = scratch(ctx, T_WORDS, 64, &words);
+    rc = scratch<T_WORDS>(ctx, 64, &words);
     if (rc) return rc;
-    TCHK(hipMemsetAsync(words, 0, 64, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, 64, st));
     tlaunch(ctx, traj_gather, dim3(blocks_for(m)), dim3(kTB), 0, st, x, y, reinterpret_cast<const long long*>(ts),
             (unsigned)n, perm, (unsigned)m, out_x, out_y, reinterpret_cast<long long*>(out_ts), words);
     return index_check(ctx, words, st, "geohip_traj_gather");
@@ -640,16 +621,16 @@ int geohip_traj_selected(geohip_ctx* ctx, const uint32_t* traj_of, uint64_t n, u
     const rocprim::counting_iterator<unsigned> iota(0u);
     const IsSelected pred{traj_of};
     size_t tb = 0;
-    TCHK(rocprim::select(nullptr, tb, iota, out_idx, (unsigned*)nullptr, n, pred, st));
+    GEOHIP_CHK(rocprim::select(nullptr, tb, iota, out_idx, (unsigned*)nullptr, n, pred, st));
     unsigned* words;
     void* temp;
-    rc = scratch(ctx, T_WORDS, 64, &words);
-    if (!rc) rc = scratch(ctx, T_TEMP, tb + 16, &temp);
+    rc = scratch<T_WORDS>(ctx, 64, &words);
+    if (!rc) rc = scratch<T_TEMP>(ctx, tb + 16, &temp);
     if (rc) return rc;
-    TCHK(rocprim::select(temp, tb, iota, out_idx, words, n, pred, st));
+    GEOHIP_CHK(rocprim::select(temp, tb, iota, out_idx, words, n, pred, st));
     uint64_t* pin = ctx_pinned(ctx);
-    TCHK(hipMemcpyAsync(pin, words, 4, hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipMemcpyAsync(pin, words, 4, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     *out_count = pin[0] & 0xffffffffu;
     return GEOHIP_OK;
 }

@@ -43,22 +43,17 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "geohip.h"
-#include "join.h"
-#include "locate.h"
+#include "traj_common.h"
 #include "trange.h"
 
 namespace geohip {
 namespace {
 
-constexpr unsigned kNone = 0xffffffffu;
-constexpr int kTB = 256;
-constexpr int kWaves = kTB / 64;
 constexpr int kQueue = 128;          // per-wave queue of points whose cell is in the set
 constexpr unsigned kLaneSegs = 48;   // longer crossing lists are walked by the whole wave
 constexpr unsigned kWaveBatches = 8;  // consecutive 64-point batches a wave takes at a time
-constexpr uint64_t kMaxGroup = 1ull << 30;  // geohip_traj_group's bound on points and trajectories
 
-// scratch slots (ctx_ensure; a call owns them for its own duration on the ctx stream)
+// scratch slots (kCallSlots, traj_common.h)
 enum RSlot { R_FLAG, R_NEWID, R_LEN, R_NEWOFF, R_TEMP = 6, R_WORDS = 7 };
 
 // words block: [0] error bits, [1] class-2 points
@@ -397,22 +392,6 @@ __global__ void __launch_bounds__(kTB) hit_perm(const unsigned* __restrict__ per
 }
 
 // ---- host side --------------------------------------------------------------------------------
-#define RCHK(expr)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return ctx_fail(ctx, GEOHIP_ERR_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-inline unsigned blocks_for(uint64_t n) { return (unsigned)((n + kTB - 1) / kTB); }
-
-template <typename T>
-int scratch(geohip_ctx* ctx, RSlot slot, size_t bytes, T** out) {
-    void* p = nullptr;
-    const int rc = ctx_ensure(ctx, slot, bytes, &p);
-    *out = static_cast<T*>(p);
-    return rc;
-}
-
 // The ctx's plan of its last polygon set: a continuous query classifies every window against the
 // same polygons, so the host planning and the upload happen once; later calls compare their
 // inputs bitwise with the cached copies.
@@ -570,16 +549,16 @@ int prepare_polygons(geohip_ctx* ctx, const geohip_grid& g, const uint32_t* poly
     if (sz_s) memcpy(host.data() + c->off_slab, slabs.data(), sz_s);
     hipStream_t st = ctx_stream(ctx);
     if (c->dev) {
-        RCHK(hipStreamSynchronize(st));  // the previous call's kernel may still read the old tables
-        RCHK(hipFree(c->dev));
+        GEOHIP_CHK(hipStreamSynchronize(st));  // the previous call's kernel may still read the old tables
+        GEOHIP_CHK(hipFree(c->dev));
         c->dev = nullptr;
     }
     if (hipMalloc(&c->dev, total) != hipSuccess) {
         c->dev = nullptr;
         return ctx_fail(ctx, GEOHIP_ERR_OOM, "polygon tables: out of device memory");
     }
-    RCHK(hipMemcpyAsync(c->dev, host.data(), total, hipMemcpyHostToDevice, st));
-    RCHK(hipStreamSynchronize(st));  // host is a local
+    GEOHIP_CHK(hipMemcpyAsync(c->dev, host.data(), total, hipMemcpyHostToDevice, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));  // host is a local
     c->grid = g;
     c->plan_budget = c->budget;
     c->npoly = npoly;
@@ -629,7 +608,7 @@ int geohip_trange_classify(geohip_ctx* ctx, const geohip_grid* grid, const doubl
         std::string err;
         rc = plan_trange(*grid, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, &err);  // the grid's checks
         if (rc) return ctx_fail(ctx, rc, err);
-        if (n) RCHK(hipMemsetAsync(out_class, 0, n, st));
+        if (n) GEOHIP_CHK(hipMemsetAsync(out_class, 0, n, st));
         return GEOHIP_OK;
     }
     if (!ring_off || !vx || !vy) return ctx_fail(ctx, GEOHIP_ERR_ARG, "null polygon arrays");
@@ -638,9 +617,9 @@ int geohip_trange_classify(geohip_ctx* ctx, const geohip_grid* grid, const doubl
     if (rc) return rc;
     if (n == 0) return GEOHIP_OK;
     unsigned* words;
-    rc = scratch(ctx, R_WORDS, 64, &words);
+    rc = scratch<R_WORDS>(ctx, 64, &words);
     if (rc) return rc;
-    RCHK(hipMemsetAsync(words, 0, 64, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, 64, st));
     const char* d = static_cast<const char*>(c->dev);
     TRArgs a;
     memset(&a, 0, sizeof a);
@@ -675,10 +654,10 @@ int geohip_trange_classify(geohip_ctx* ctx, const geohip_grid* grid, const doubl
     const uint64_t want = (runs + kWaves - 1) / kWaves;
     const unsigned grid_blocks = (unsigned)std::min<uint64_t>(want, (uint64_t)ctx_cus(ctx) * (uint64_t)resident);
     tlaunch(ctx, trange_classify, dim3(grid_blocks), dim3(kTB), 0, st, a);
-    RCHK(hipGetLastError());
+    GEOHIP_CHK(hipGetLastError());
     uint64_t* pin = ctx_pinned(ctx);
-    RCHK(hipMemcpyAsync(pin, words, 8, hipMemcpyDeviceToHost, st));
-    RCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipMemcpyAsync(pin, words, 8, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     const uint64_t count = pin[0] >> 32;
     *out_count = count;
     if (!out_idx && cap == 0) return GEOHIP_OK;  // classes only
@@ -688,12 +667,12 @@ int geohip_trange_classify(geohip_ctx* ctx, const geohip_grid* grid, const doubl
     const rocprim::counting_iterator<unsigned> iota(0u);
     const IsContained pred{out_class};
     size_t tb = 0;
-    RCHK(rocprim::select(nullptr, tb, iota, out_idx, (unsigned*)nullptr, n, pred, st));
+    GEOHIP_CHK(rocprim::select(nullptr, tb, iota, out_idx, (unsigned*)nullptr, n, pred, st));
     void* temp;
-    rc = scratch(ctx, R_TEMP, tb + 16, &temp);
+    rc = scratch<R_TEMP>(ctx, tb + 16, &temp);
     if (rc) return rc;
-    RCHK(rocprim::select(temp, tb, iota, out_idx, words + 2, n, pred, st));
-    RCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(rocprim::select(temp, tb, iota, out_idx, words + 2, n, pred, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     return GEOHIP_OK;
 }
 
@@ -716,7 +695,7 @@ int geohip_traj_filter_hit(geohip_ctx* ctx, const uint32_t* traj_of, const uint3
     *n_hit_traj = 0;
     *n_hit_sel = 0;
     if (ctx_mem(ctx) != GEOHIP_MEM_DEVICE) return ctx_fail(ctx, GEOHIP_ERR_ARG, "geohip_traj_filter_hit takes device memory");
-    if (n > kMaxGroup || n_sel > kMaxGroup || n_traj > kMaxGroup) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "more than 2^30 points");
+    if (n > kMaxPoints || n_sel > kMaxPoints || n_traj > kMaxPoints) return ctx_fail(ctx, GEOHIP_ERR_UNSUPPORTED, "more than 2^30 points");
     if (n_sel > n || n_traj > n_sel) return ctx_fail(ctx, GEOHIP_ERR_ARG, "n_traj <= n_sel <= n does not hold");
     if (!out_traj_off || (n && (!traj_of || !cls || !out_traj_of)) ||
         (n_traj && (!traj_first || !traj_off || !perm || !out_traj_first || !out_perm || !hit_traj)))
@@ -724,37 +703,37 @@ int geohip_traj_filter_hit(geohip_ctx* ctx, const uint32_t* traj_of, const uint3
     hipStream_t st = ctx_stream(ctx);
     const unsigned nn = (unsigned)n, T = (unsigned)n_traj, ns = (unsigned)n_sel;
     if (T == 0) {
-        RCHK(hipMemsetAsync(out_traj_off, 0, 4, st));
-        if (n) RCHK(hipMemsetAsync(out_traj_of, 0xff, n * 4, st));
+        GEOHIP_CHK(hipMemsetAsync(out_traj_off, 0, 4, st));
+        if (n) GEOHIP_CHK(hipMemsetAsync(out_traj_of, 0xff, n * 4, st));
         return GEOHIP_OK;
     }
     size_t tb = 0;
-    RCHK(rocprim::exclusive_scan(nullptr, tb, (unsigned*)nullptr, (unsigned*)nullptr, 0u, (size_t)T + 1,
-                                 rocprim::plus<unsigned>(), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(nullptr, tb, (unsigned*)nullptr, (unsigned*)nullptr, 0u, (size_t)T + 1,
+                                       rocprim::plus<unsigned>(), st));
     unsigned *flag, *newid, *len, *newoff, *words;
     void* temp;
     const size_t tw = ((size_t)T + 1) * 4;
-    rc = scratch(ctx, R_FLAG, tw, &flag);
-    if (!rc) rc = scratch(ctx, R_NEWID, tw, &newid);
-    if (!rc) rc = scratch(ctx, R_LEN, tw, &len);
-    if (!rc) rc = scratch(ctx, R_NEWOFF, tw, &newoff);
-    if (!rc) rc = scratch(ctx, R_TEMP, tb + 16, &temp);
-    if (!rc) rc = scratch(ctx, R_WORDS, 64, &words);
+    rc = scratch<R_FLAG>(ctx, tw, &flag);
+    if (!rc) rc = scratch<R_NEWID>(ctx, tw, &newid);
+    if (!rc) rc = scratch<R_LEN>(ctx, tw, &len);
+    if (!rc) rc = scratch<R_NEWOFF>(ctx, tw, &newoff);
+    if (!rc) rc = scratch<R_TEMP>(ctx, tb + 16, &temp);
+    if (!rc) rc = scratch<R_WORDS>(ctx, 64, &words);
     if (rc) return rc;
-    RCHK(hipMemsetAsync(flag, 0, tw, st));
-    RCHK(hipMemsetAsync(words, 0, 64, st));
+    GEOHIP_CHK(hipMemsetAsync(flag, 0, tw, st));
+    GEOHIP_CHK(hipMemsetAsync(words, 0, 64, st));
     tlaunch(ctx, hit_mark, dim3(blocks_for(n)), dim3(kTB), 0, st, traj_of, cls, nn, T, (unsigned)threshold, flag, words);
     tlaunch(ctx, hit_lengths, dim3(blocks_for((uint64_t)T + 1)), dim3(kTB), 0, st, traj_off, T, ns, flag, len, words);
     size_t tb2 = tb;
-    RCHK(rocprim::exclusive_scan(temp, tb2, flag, newid, 0u, (size_t)T + 1, rocprim::plus<unsigned>(), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(temp, tb2, flag, newid, 0u, (size_t)T + 1, rocprim::plus<unsigned>(), st));
     tb2 = tb;
-    RCHK(rocprim::exclusive_scan(temp, tb2, len, newoff, 0u, (size_t)T + 1, rocprim::plus<unsigned>(), st));
+    GEOHIP_CHK(rocprim::exclusive_scan(temp, tb2, len, newoff, 0u, (size_t)T + 1, rocprim::plus<unsigned>(), st));
     uint64_t* pin = ctx_pinned(ctx);
-    RCHK(hipGetLastError());
-    RCHK(hipMemcpyAsync(pin, words, 4, hipMemcpyDeviceToHost, st));
-    RCHK(hipMemcpyAsync(pin + 1, newid + T, 4, hipMemcpyDeviceToHost, st));
-    RCHK(hipMemcpyAsync(pin + 2, newoff + T, 4, hipMemcpyDeviceToHost, st));
-    RCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipGetLastError());
+    GEOHIP_CHK(hipMemcpyAsync(pin, words, 4, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipMemcpyAsync(pin + 1, newid + T, 4, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipMemcpyAsync(pin + 2, newoff + T, 4, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     const char* bad = "geohip_traj_filter_hit: traj_of entry >= n_traj, perm entry >= n or outside its trajectory's "
                       "slice, or traj_off not ascending or past n_sel";
     if ((pin[0] & 0xffffffffu) & kErrIndex) return ctx_fail(ctx, GEOHIP_ERR_ARG, bad);
@@ -767,9 +746,9 @@ int geohip_traj_filter_hit(geohip_ctx* ctx, const uint32_t* traj_of, const uint3
     if (ns)
         tlaunch(ctx, hit_perm, dim3(blocks_for(n_sel)), dim3(kTB), 0, st, perm, traj_of, traj_off, (const unsigned*)flag,
                 (const unsigned*)newoff, nn, ns, out_perm, words);
-    RCHK(hipGetLastError());
-    RCHK(hipMemcpyAsync(pin, words, 4, hipMemcpyDeviceToHost, st));
-    RCHK(hipStreamSynchronize(st));
+    GEOHIP_CHK(hipGetLastError());
+    GEOHIP_CHK(hipMemcpyAsync(pin, words, 4, hipMemcpyDeviceToHost, st));
+    GEOHIP_CHK(hipStreamSynchronize(st));
     if ((pin[0] & 0xffffffffu) & kErrIndex) return ctx_fail(ctx, GEOHIP_ERR_ARG, bad);
     *n_hit_traj = Th;
     *n_hit_sel = nh;
