@@ -1,5 +1,7 @@
 """Phase timeline of one kNN pass launch (100 MHz timestamps): per-block start, stream end,
-flush (block barrier), stores drained, arrived; the last block's acquire, gather and write.
+slot bound built (tb: before the block barrier, by the first wave out of the stream loop), flush
+(block barrier), stores drained, arrived; the last block's acquire, gather and write, its own
+chain from its flush on (last_chain, each phase's length) and which final ran.
 Percentiles (0, 10, 50, 90, 100) in microseconds relative to the earliest block start (GPU box
 measurement)."""
 import json
@@ -30,7 +32,7 @@ for w in range(W):
     ys.append(y)
 torch.cuda.synchronize()
 names = ["start", "stream_end", "flush", "drained", "arrived"] + (["lookback", "emitted"] if ABL < 0 else [])
-blk = {"hist": 8, "listed": 9, "heads": 10}
+blk = {"tb": 14, "hist": 8, "listed": 9, "heads": 10}
 fin = {"acquired": 5, "loaded": 11, "T": 12, "taken": 13, "gathered": 6, "written": 7}
 out = {}
 for rep in range(4):
@@ -46,8 +48,20 @@ for rep in range(4):
                            for nm, j in blk.items()}
     row["blocks_reached"] = {nm: int((tr[:, j] != 0).sum()) for nm, j in blk.items()}
     last = int(np.argmax(tr[:, 7]))
-    row["final"] = {nm: round(float(rel[last, j]), 2) for nm, j in fin.items()}
+    # (None: not reached -- the direct final stamps no "taken")
+    row["final"] = {nm: (round(float(rel[last, j]), 2) if tr[last, j] else None) for nm, j in fin.items()}
     row["last_block"] = last
+    # the last block's own dependent chain after its last byte: flush -> record stored (heads) ->
+    # drained -> arrived -> acquired -> loaded -> gathered -> written; tb_before_flush: how long
+    # before its barrier its slot bound stood
+    chain = [("flush", 2), ("heads", 10), ("drained", 3), ("arrived", 4), ("acquired", 5), ("loaded", 11),
+             ("gathered", 6), ("written", 7)]
+    row["last_chain"] = {f"{a}->{b}": round(float(rel[last, j] - rel[last, i]), 2)
+                         for (a, i), (b, j) in zip(chain[:-1], chain[1:])}
+    row["last_chain"]["flush->written"] = round(float(rel[last, 7] - rel[last, 2]), 2)
+    row["last_chain"]["tb_before_flush"] = round(float(rel[last, 2] - rel[last, 14]), 2) if tr[last, 14] else None
+    end = ctx.debug_knn_pass_end()
+    row["final_ran"] = {1: "direct", 2: "T"}.get(end, end)
     row["stats"] = ctx.debug_knn_pass_stats()
     out[f"rep{rep}"] = row
 print(json.dumps({"shape": dict(n=n, k=K, r=R, grid=GN, ablation=ABL), **out}))

@@ -285,6 +285,7 @@ _SIGS = {
     "geohip_debug_selftest_fp64": (c_int, [_P, _P, _P, c_uint64, _P, _P, _P, _P]),
     "geohip_debug_classify": (c_int, [POINTER(Grid), c_double, c_double, c_double, _P, _P, c_uint64, _P]),
     "geohip_debug_knn_pass_stats": (c_int, [_P, _P]),
+    "geohip_debug_knn_pass_end": (c_int, [_P, _P]),
     "geohip_debug_knn_pass_trace": (c_int, [_P, POINTER(Grid), _P, _P, c_uint64, c_double, c_double, c_double,
                                             c_uint32, c_int, _P, c_uint64, POINTER(c_uint32)]),
 }
@@ -1404,6 +1405,15 @@ class Context:
         out = np.zeros(3, dtype=np.uint32)
         self._check(lib.geohip_debug_knn_pass_stats(self.h, out.ctypes.data_as(c_void_p)), "debug_knn_pass_stats")
         return tuple(int(v) for v in out)
+
+    FINAL_DIRECT, FINAL_T = 1, 2
+
+    def debug_knn_pass_end(self):
+        """Which final the last kNN pass ran: FINAL_DIRECT from the blocks' records or FINAL_T
+        through the heads' histogram (the entry's second word is unused)."""
+        out = np.zeros(2, dtype=np.uint32)
+        self._check(lib.geohip_debug_knn_pass_end(self.h, out.ctypes.data_as(c_void_p)), "debug_knn_pass_end")
+        return int(out[0])
 
     def debug_knn_pass_trace(self, grid, x, y, qx, qy, r, k, ablation=0):
         """One traced kNN pass on device x/y: [nblocks, 8] timestamps (100 MHz, 0 = not reached)."""

@@ -1293,9 +1293,23 @@ int geohip_debug_knn_pass_stats(geohip_ctx* ctx, uint32_t* out3) {
     return GEOHIP_OK;
 }
 
+// Test hook: how the last kNN pass ended its window, read back after a synchronise: out2[0] =
+// which final ran (1 direct from the blocks' records, 2 through the heads' histogram and T),
+// out2[1] is unused (0: every block publishes its record once).
+int geohip_debug_knn_pass_end(geohip_ctx* ctx, uint32_t* out2) {
+    int rc = begin(ctx);
+    if (rc) return rc;
+    if (!ctx->buf[S_SPILL_CNT]) return fail(ctx, GEOHIP_ERR_ARG, "no kNN pass ran");
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(out2, B<char>(ctx, S_SPILL_CNT) + kKnnCounterBytes - 64 + 4 * kKnnFinalWord, 8,
+                     hipMemcpyDeviceToHost));
+    return GEOHIP_OK;
+}
+
 // Measurement hook: one kNN pass (device memory) with per-block phase timestamps (100 MHz):
 // host[16 b + s], s = start, stream end, flush, stores drained, arrived; the last block also
-// acquired, gathered, written.  *nblocks = blocks of the launch.
+// acquired, gathered, written; s = 14: the slot bound T_b built (before the block barrier, by the
+// first wave to leave the stream loop).  *nblocks = blocks of the launch.
 int geohip_debug_knn_pass_trace(geohip_ctx* ctx, const geohip_grid* grid, const double* x, const double* y,
                                 uint64_t n, double qx, double qy, double r, uint32_t k, int ablation, uint64_t* host,
                                 uint64_t cap_words, unsigned* nblocks) {

@@ -34,8 +34,13 @@ constexpr unsigned kGhistWord = kTicketStride * (kMaxTicketGroups + 2);
 constexpr int kGhistCopies = 8;
 constexpr size_t kKnnCounterBytes = 32768;
 // kNN pass (one launch per window; k <= GEOHIP_KNN_MAX_K): list_d/list_i hold
-// knn_pass_list_entries(nblocks) entries (block lists, packed heads, lengths), spill_d/spill_i
-// n entries, ctr is the kKnnCounterBytes zeroed counter scratch (re-armed by every launch).
+// knn_pass_list_entries(nblocks) entries (block lists; in list_d, after them, one 128-byte record
+// per block: heads or slots, their indices, the length word), spill_d/spill_i n entries, ctr is
+// the kKnnCounterBytes zeroed counter scratch (re-armed by every launch).  The last 16 words of
+// ctr are the last final's figures: entries gathered, spilled, kept, which final ran
+// (kKnnFinalWord: 1 direct from the records, 2 through the heads' histogram and T), then an
+// unused word (0: every block publishes once, after its barrier).
+constexpr unsigned kKnnFinalWord = 3;  // word of the figures holding which final ran
 void knn_pass_geometry(uint64_t n, unsigned* nblocks, uint64_t* chunk);
 size_t knn_pass_list_entries(unsigned nblocks);
 // The range query of the same point fused into the pass (see knn_pass; status = kPassMaxBlocks

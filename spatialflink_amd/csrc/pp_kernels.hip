@@ -683,11 +683,11 @@ __device__ __forceinline__ void ticket_zero(unsigned* p) {
 // distance histogram in LDS (B = upper edge of the bin where the block's cumulative count
 // reaches k: at least k real points at or below it).  At its end a block
 //  * writes its survivors <= B to its list slot unsorted (ballot + LDS cursor, write-through),
-//  * writes its 4 smallest sorted (heads, packed for coalesced reads) and its list length,
+//  * writes its smallest sorted (heads) and its list length into its record (one 128-byte line),
 // and takes a 2-level arrival ticket.  The last block to arrive (Guideline 16 counter hand-off)
-// loads the 4 heads of every block, takes T = upper edge of the bin where their cumulative count
+// loads the record of every block (its 8 heads), takes T = upper edge of the bin where their cumulative count
 // reaches k (>= k real points at or below it, so T bounds the window's k-th key), keeps the
-// heads <= T, reads the whole list of the rare block whose 4 heads all pass, places the kept
+// heads <= T, reads the whole list of the rare block whose heads all pass, places the kept
 // entries by rank and writes the k smallest.  No separate final launch, no sorted block lists.
 constexpr int kPassNW = 16;                     // waves per block
 constexpr unsigned kPassMaxBlocks = 256;        // one block per CU
@@ -699,11 +699,14 @@ constexpr unsigned kLenSlots = 0x40000000u;     // list length flag: the block's
 // bounds the distance of a real point of the block, distinct blocks hold distinct points, so the
 // upper edge of the bin where k of the published bins have accumulated bounds the window's k-th
 // distance.  A block whose survivors at or below that bound T_b fit kPassHeads slots writes
-// just those (its share of the window's k nearest is among them) and skips the list / head
-// ranking; the last block re-arms the words.
+// just those into its record (its share of the window's k nearest is among them; one store
+// instruction, nothing into its list region) and skips the list / head ranking; the last block
+// re-arms the words.
 constexpr unsigned kSlotMaxK = 256;
 constexpr unsigned kMinWord = 6400;
-constexpr unsigned kStatWord = (unsigned)(kKnnCounterBytes / 4) - 16;  // last final: entries, spilled, kept
+constexpr unsigned kStatWord = (unsigned)(kKnnCounterBytes / 4) - 16;  // last final: entries, spilled, kept,
+                                                                       // which final ran (below)
+constexpr unsigned kFinalDirect = 1u, kFinalT = 2u;
 constexpr unsigned kVbWord = kTicketStride * (kMaxTicketGroups + 1);      // chunk ticket (fused range)
 
 template <int NW>
@@ -723,6 +726,7 @@ struct PassBlock {
     unsigned fin[4];            // the final's LDS words
     unsigned long long tslot;   // slot bound T_b (kSentinelD: none)
     unsigned nslot;             // survivors at or below T_b
+    unsigned left;              // waves that have left the stream loop (the first one builds T_b)
 };
 
 // One wave: the lowest bin holding a survivor, -1 if none (8 bins per lane).
@@ -741,9 +745,7 @@ struct PassIo {
     unsigned long long* list_d;  // block b: [b * list_cap, b * list_cap + len[b])
     unsigned* list_i;
     unsigned list_cap;
-    unsigned long long* head_d;  // block b: [kPassHeads * b, + kPassHeads), sentinel-padded
-    unsigned* head_i;
-    unsigned* len;               // nblocks list lengths
+    unsigned long long* rec;     // block b's record: kRecWords 64-bit words at [kRecWords * b] (below)
     unsigned long long* spill_d;
     unsigned long long* spill_d_unused;
     unsigned* spill_i;
@@ -754,9 +756,40 @@ struct PassIo {
     unsigned groups;
     unsigned long long* trace;   // measurement only: 8 timestamps per block (null in production)
 };
+// A block's record: one 128-byte line -- its kPassHeads heads (or slots) as 8 distance words,
+// 8 index words (sentinel-padded) and the list length / flag word; 28 bytes unused.  The final
+// fetches one line per block, and a slot-complete block publishes with one store instruction.
+constexpr unsigned kRecWords = 16;  // 64-bit words per record
+static_assert(kPassHeads * 8 + kPassHeads * 4 + 4 <= kRecWords * 8, "a record holds heads, indices and length");
+__device__ __forceinline__ unsigned long long* rec_d(const PassIo& io, unsigned b) {
+    return io.rec + (size_t)kRecWords * b;
+}
+__device__ __forceinline__ unsigned* rec_i(const PassIo& io, unsigned b) {
+    return reinterpret_cast<unsigned*>(io.rec + (size_t)kRecWords * b + kPassHeads);
+}
+__device__ __forceinline__ unsigned* rec_len(const PassIo& io, unsigned b) {
+    return reinterpret_cast<unsigned*>(io.rec + (size_t)kRecWords * b + kPassHeads + kPassHeads / 2);
+}
+// Entry q of block b's list (q below its masked length): a slot-complete block (kLenSlots) keeps
+// its entries in its record alone, every other block in its list region.
+__device__ __forceinline__ void list_entry(const PassIo& io, unsigned b, unsigned lenword, unsigned q,
+                                           unsigned long long& d, unsigned& i) {
+    if (lenword & kLenSlots) {
+        d = rec_d(io, b)[q];
+        i = rec_i(io, b)[q];
+    } else {
+        d = io.list_d[(size_t)b * io.list_cap + q];
+        i = io.list_i[(size_t)b * io.list_cap + q];
+    }
+}
 #define PASS_TRACE(io, slot)                                                                      \
     do {                                                                                          \
         if ((io).trace && threadIdx.x == 0) (io).trace[16 * (size_t)blockIdx.x + (slot)] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
+// the same from whichever wave runs the phase (its first lane)
+#define PASS_TRACE_WAVE(io, slot)                                                                 \
+    do {                                                                                          \
+        if ((io).trace && lane_id() == 0) (io).trace[16 * (size_t)blockIdx.x + (slot)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 
 // exact distances of up to 64 staged candidates; survivors (<= the block bound) appended to the
@@ -849,9 +882,11 @@ __device__ __forceinline__ void wave_kmin(unsigned long long& d, unsigned& i) {
 }
 
 // The window's k smallest, run by the last block (NT = 1024 threads).  Latency-bound: every
-// dependent LDS round trip costs ~35 ns and a global one ~1 us, so the phases are few and wide:
-//   A  loads: every block's 8 packed heads (2 per thread), its list length and last head (thread
-//      b stands for block b), the spill count;
+// dependent LDS round trip costs ~35 ns and a global one ~1 us, so the phases are few and wide.
+// When every block is slot-complete and nothing spilled (the common case of a large window) the
+// direct final below takes the answer from the records alone; else the T path:
+//   A  loads: every block's record -- its 8 heads (2 per thread), its list length and last head
+//      (thread b stands for block b) -- and the spill count;
 //   B  the heads' distance histogram (LDS atomics) and, per block, "read whole": its 8th head
 //      beats T or its heads are flagged incomplete -- known only after T, so the blocks' last
 //      heads go to LDS;
@@ -867,20 +902,100 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
     const int lane = lane_id(), wid = threadIdx.x / kWave;
     constexpr unsigned kPer = kPassMaxBlocks * kPassHeads / NT;
     static_assert(kPer == 2, "final: 2 heads per thread");
-    // ---- A: loads up front
+    // ---- A: loads up front (one 128-byte record per block)
     const unsigned nspill = load_sc1(io.ctr);
     unsigned long long hd[kPer];
     unsigned hi[kPer];
 #pragma unroll
     for (unsigned u = 0; u < kPer; u++) {
         const unsigned t = threadIdx.x + u * NT;
-        const bool ok = t < kPassHeads * nb;
-        hd[u] = ok ? io.head_d[t] : kSentinelD;
-        hi[u] = ok ? io.head_i[t] : kSentinelI;
+        const unsigned b = t / kPassHeads, h = t % kPassHeads;
+        const bool ok = b < nb;
+        hd[u] = ok ? rec_d(io, b)[h] : kSentinelD;
+        hi[u] = ok ? rec_i(io, b)[h] : kSentinelI;
     }
     const bool blk = threadIdx.x < nb;  // thread b also stands for block b
-    const unsigned mylen = blk ? io.len[threadIdx.x] : 0u;
-    const unsigned long long blast = blk ? io.head_d[kPassHeads * threadIdx.x + kPassHeads - 1] : kSentinelD;
+    const unsigned mylen = blk ? *rec_len(io, threadIdx.x) : 0u;
+    const unsigned long long blast = blk ? rec_d(io, threadIdx.x)[kPassHeads - 1] : kSentinelD;
+    if (blk) io.ctr[kMinWord + threadIdx.x] = 0u;  // slot-bound words re-armed for the next launch (either path)
+    auto put = [&](unsigned pos, unsigned long long d, unsigned i) {
+        io.out_d[pos] = __longlong_as_double((long long)d);
+        io.out_i[pos] = i;
+    };
+    // sentinel padding, the count, and the counter words re-armed for the next window on this
+    // stream: the spill count and the chunk ticket (fused range); the arrival tickets were
+    // re-armed by their last arrivals (pass_arrive_last), the slot-bound words above
+    auto finish = [&](unsigned outn) {
+        for (unsigned t = outn + threadIdx.x; t < k; t += NT) put(t, kSentinelD, kSentinelI);
+        if (threadIdx.x == 0) {
+            *io.out_count = outn;
+            store_wt(io.ctr, 0u);
+            store_wt(io.ctr + kVbWord, 0u);
+        }
+    };
+    // ---- direct final: every block slot-complete and nothing spilled.  A block's slots hold
+    // every survivor of it at or below a valid bound of the window's k-th distance, so the
+    // window's k smallest are among the records' real entries (at most kPassHeads per block).
+    // There are several times k of them (C2: 350-410 for k = 50, each block keeps what its own,
+    // looser bound T_b admits), and ranking them all costs ~20 us (m^2 64-bit key compares on one
+    // CU), so the entries still pass a bound first: their histogram goes up as the loads arrive
+    // (zeroed beforehand: no barrier between the loads' issue and their use), one wave takes T
+    // from it, every thread keeps its entries at or below T (ballot, one LDS atomic per wave)
+    // and all rank the ~k kept: three barriers where the T path has five, and no list lengths,
+    // last heads or whole-list verdicts.  A vetoed window goes through the T path below,
+    // unchanged.  hist, sh[1] (veto) and sh[2] (cursor) were zeroed by the caller before its
+    // last barrier.
+    {
+        const bool veto = (blk && !(mylen & kLenSlots)) || nspill != 0u;
+        if (__ballot(veto) && lane == 0) sh[1] = 1u;
+#pragma unroll
+        for (unsigned u = 0; u < kPer; u++)
+            if (hd[u] != kSentinelD) atomicAdd(&hist[hist_bin(hd[u], a.hist_base)], 1u);
+        __syncthreads();
+        PASS_TRACE(io, 11);
+        if (sh[1] == 0u) {
+            // (every wave scanning the histogram for itself, to save this barrier, measured
+            // slower: 16 scans share 4 SIMDs, acquired -> T 1.96 us against 1.4)
+            if (wid == 0) {
+                const int bin = hist_kth_bin(hist, k);
+                if (lane == 0) sh[0] = (bin >= 0 && bin < kHistBins - 1) ? (unsigned)bin : 0xffffffffu;
+            }
+            __syncthreads();
+            PASS_TRACE(io, 12);
+            const unsigned long long T = sh[0] != 0xffffffffu ? hist_edge((int)sh[0], a.hist_base) : kSentinelD;
+            const bool r0 = hd[0] != kSentinelD && hd[0] <= T, r1 = hd[1] != kSentinelD && hd[1] <= T;
+            const unsigned long long m0 = __ballot(r0), m1 = __ballot(r1);
+            const unsigned c0 = (unsigned)__popcll(m0), c1 = (unsigned)__popcll(m1);
+            if (c0 + c1) {
+                unsigned base = 0;
+                if (lane == 0) base = atomicAdd(&sh[2], c0 + c1);
+                base = __shfl(base, 0);
+                const unsigned p0 = base + lanes_below(m0), p1 = base + c0 + lanes_below(m1);
+                if (r0 && p0 < gcap) {
+                    gd[p0] = hd[0];
+                    gi[p0] = hi[0];
+                }
+                if (r1 && p1 < gcap) {
+                    gd[p1] = hd[1];
+                    gi[p1] = hi[1];
+                }
+            }
+            __syncthreads();
+            const unsigned m = sh[2];  // at most kPassHeads entries per block: within gcap and 2 NT (asserted by the caller)
+            if (threadIdx.x == 0) {
+                io.ctr[kStatWord] = 0u;
+                io.ctr[kStatWord + 1] = 0u;
+                io.ctr[kStatWord + 2] = m;
+                io.ctr[kStatWord + kKnnFinalWord] = kFinalDirect;
+            }
+            PASS_TRACE(io, 6);
+            rank_place<NT>(gd, gi, m, k, put);
+            finish(m < k ? m : k);
+            return;
+        }
+    }
+    // ---- the T path: some block listed, or something spilled (nobody reads hist or the cursor
+    // on this side of the verdict, so they are re-armed at once)
     for (unsigned t = threadIdx.x; t < kHistBins; t += NT) hist[t] = 0;
     if (threadIdx.x == 0) {
         sh[0] = 0xffffffffu;  // T bin
@@ -896,9 +1011,8 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
     if (blk) {
         // flagged: whole whatever T; slot-complete: never (its slots hold all it contributes)
         blast_sh[threadIdx.x] = (mylen & kLenWhole) ? 0ull : ((mylen & kLenSlots) ? kSentinelD : blast);
-        lens[threadIdx.x] = mylen & ~(kLenWhole | kLenSlots);
+        lens[threadIdx.x] = mylen;  // with its flags: list_entry reads a kLenSlots block's record
     }
-    if (blk) io.ctr[kMinWord + threadIdx.x] = 0u;  // slot-bound words re-armed for the next launch
     __syncthreads();
     // ---- C
     if (wid == 0) {
@@ -942,15 +1056,13 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
     const unsigned nwhole = sh[3];
     for (unsigned w = (unsigned)wid; w < nwhole; w += NT / kWave) {  // one wave per whole list
         const unsigned b = wl[w];
-        const unsigned L = lens[b];
+        const unsigned lw = lens[b];
+        const unsigned L = lw & ~(kLenWhole | kLenSlots);
         for (unsigned q0 = 0; q0 < L; q0 += kWave) {
             const unsigned q = q0 + (unsigned)lane;
             unsigned long long d = kSentinelD;
             unsigned i = kSentinelI;
-            if (q < L) {
-                d = io.list_d[(size_t)b * io.list_cap + q];
-                i = io.list_i[(size_t)b * io.list_cap + q];
-            }
+            if (q < L) list_entry(io, b, lw, q, d, i);
             take(q < L, d, i);
         }
     }
@@ -970,12 +1082,9 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
         io.ctr[kStatWord] = nwhole;
         io.ctr[kStatWord + 1] = nspill;
         io.ctr[kStatWord + 2] = m;
+        io.ctr[kStatWord + kKnnFinalWord] = kFinalT;
     }
     PASS_TRACE(io, 6);
-    auto put = [&](unsigned pos, unsigned long long d, unsigned i) {
-        io.out_d[pos] = __longlong_as_double((long long)d);
-        io.out_i[pos] = i;
-    };
     unsigned outn = m < k ? m : k;
     if (m <= 2u * NT) {
         rank_place<NT>(gd, gi, m, k, put);
@@ -1004,11 +1113,11 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
                 unsigned long long ed = kSentinelD;
                 unsigned ei = kSentinelI;
                 if (t < nl) {
-                    // (a slot-complete block's length word carries kLenSlots: its list holds its slots)
-                    if (t % io.list_cap < (io.len[t / io.list_cap] & ~(kLenWhole | kLenSlots))) {
-                        ed = io.list_d[t];
-                        ei = io.list_i[t];
-                    }
+                    // (the length word's flags masked out; a slot-complete block's entries are in
+                    // its record, its list region holds whatever an earlier launch left there)
+                    const unsigned b = (unsigned)(t / io.list_cap), q = (unsigned)(t % io.list_cap);
+                    const unsigned lw = lens[b];
+                    if (q < (lw & ~(kLenWhole | kLenSlots))) list_entry(io, b, lw, q, ed, ei);
                 } else {
                     ed = io.spill_d[t - nl];
                     ei = io.spill_i[t - nl];
@@ -1040,12 +1149,7 @@ __device__ __forceinline__ void pass_final(const PassIo& io, const KnnArgs& a, u
         }
         outn = got;
     }
-    for (unsigned t = outn + threadIdx.x; t < k; t += NT) put(t, kSentinelD, kSentinelI);
-    if (threadIdx.x == 0) {
-        *io.out_count = outn;
-        store_wt(io.ctr, 0u);            // spill count and the chunk ticket (fused range) re-armed
-        store_wt(io.ctr + kVbWord, 0u);  // for the next window on this stream
-    }
+    finish(outn);
 }
 
 __device__ __forceinline__ bool pass_arrive_last(unsigned* tickets, unsigned G) {
@@ -1245,6 +1349,9 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
         kb.cnt = 0;
         kb.cursor = 0;
         kb.nsmall = 0;
+        kb.left = 0;
+        kb.tslot = kSentinelD;
+        kb.nslot = 0;
         kb.next_it = 2 * NW;  // iterations wid and NW + wid start statically
     }
     PASS_TRACE(io, 0);
@@ -1408,9 +1515,24 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
         }
     }
     PASS_TRACE(io, 1);
-    // the other blocks' published bins, in flight while the block's last batches finish
+    // ---- slot bound (k <= kSlotMaxK), built before the block barrier by the first wave to leave
+    // the stream loop, while the others finish: T_b = upper edge of the bin where k of the blocks'
+    // lowest survivor bins (this block's current one, the others' as published) accumulate.  The
+    // loads of the published bins are in flight while the wave flushes its last batch; the
+    // 512-word scratch histogram lives in the wave's own stage, idle once that batch is flushed
+    // (no other wave touches it).  The block's own lowest bin is read while other waves may
+    // still append: a stale (higher) bin still stands for a real survivor of the block, so T_b
+    // stays a valid bound of the window's k-th distance, at worst a looser one.  After the
+    // barrier only the extraction is left.  Waves that never had an iteration (small windows)
+    // leave at once, before the block has a survivor: they do not build.
+    bool builder = false;
+    if (slots && !(ABL & 7) && (unsigned)wid < niters) {
+        unsigned f = 0;
+        if (lane == 0) f = atomicAdd(&kb.left, 1u);
+        builder = __builtin_amdgcn_readfirstlane((int)f) == 0;
+    }
     unsigned gv[kPassMaxBlocks / kWave] = {};
-    if (slots && wid == 0) {
+    if (builder) {
 #pragma unroll
         for (unsigned u = 0; u < kPassMaxBlocks / kWave; u++) {
             const unsigned b = (unsigned)lane + u * kWave;
@@ -1418,6 +1540,26 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
         }
     }
     pass_dist_batch<PB, RANGE>(st, ccnt, kb, args, io, appended, true, rs);
+    if (builder) {
+        static_assert(sizeof(WaveStage::cx) >= kHistBins * sizeof(unsigned), "the scratch histogram fits one stage array");
+        unsigned* mh = reinterpret_cast<unsigned*>(st.cx);
+        asm volatile("" ::: "memory");
+        const int own = hist_low_bin(kb.hist);
+#pragma unroll
+        for (int j = 0; j < 8; j++) mh[lane * 8 + j] = 0u;
+        wave_lds_sync();
+#pragma unroll
+        for (unsigned u = 0; u < kPassMaxBlocks / kWave; u++) {
+            const unsigned b = (unsigned)lane + u * kWave;
+            const int bin = b == blockIdx.x ? own : (int)gv[u] - 1;
+            if (b < gridDim.x && bin >= 0 && bin < kHistBins - 1) atomicAdd(&mh[bin], 1u);
+        }
+        if (lane == 0 && own >= 0 && own < kHistBins - 1) store_wt(io.ctr + kMinWord + blockIdx.x, (unsigned)own + 1u);
+        wave_lds_sync();
+        const int tb = hist_kth_bin(mh, k);
+        if (lane == 0 && tb >= 0 && tb < kHistBins - 1) kb.tslot = hist_edge(tb, args.hist_base);
+        PASS_TRACE_WAVE(io, 14);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // spilled survivors drained before the ticket
     __syncthreads();
     PASS_TRACE(io, 2);
@@ -1433,70 +1575,85 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
     // heads, in order.  A list whose heads may be incomplete (spilled survivors counted in the
     // histogram, > 64 entries <= H) is flagged in its length word so the final reads it whole.
     // Then the arrival (cdna_hip_programming.md §6 Guideline 16, counter form): the storing wave
-    // drains its write-through stores and takes the ticket.  Common case (<= 256 survivors): wave
-    // 0 alone, in registers, behind no further barrier; else every wave through LDS.
+    // drains its write-through stores and takes the ticket.  With at most 256 survivors wave 0
+    // does all of it alone, behind no further barrier (slots and list path alike); else every
+    // wave takes part, through LDS.
     const unsigned have = kb.cnt < (unsigned)PB::kCap ? kb.cnt : (unsigned)PB::kCap;  // block-uniform
     const size_t lbase = (size_t)blockIdx.x * io.list_cap;
     // ---- slot-complete end of block (k <= kSlotMaxK): T_b = upper edge of the bin where k of
     // the blocks' lowest survivor bins (this block's current one, the others' as published)
     // accumulate; the survivors <= T_b (the spill goes to the final on its own) into the slots
+    // (wave 0 knows it where it alone extracts; block-uniform where every wave does)
     bool slotted = false;
     if (slots && !(ABL & 7)) {
-        unsigned* mh = reinterpret_cast<unsigned*>(&stage[0]);  // 512 words: the stages are idle
-        if (wid == 0) {
-            const int own = hist_low_bin(kb.hist);
-#pragma unroll
-            for (int j = 0; j < 8; j++) mh[lane * 8 + j] = 0u;
-            wave_lds_sync();
-#pragma unroll
-            for (unsigned u = 0; u < kPassMaxBlocks / kWave; u++) {
-                const unsigned b = (unsigned)lane + u * kWave;
-                const int bin = b == blockIdx.x ? own : (int)gv[u] - 1;
-                if (b < gridDim.x && bin >= 0 && bin < kHistBins - 1) atomicAdd(&mh[bin], 1u);
-            }
-            if (lane == 0 && own >= 0 && own < kHistBins - 1) store_wt(io.ctr + kMinWord + blockIdx.x, (unsigned)own + 1u);
-            wave_lds_sync();
-            const int tb = hist_kth_bin(mh, k);
-            if (lane == 0) {
-                kb.tslot = (tb >= 0 && tb < kHistBins - 1) ? hist_edge(tb, args.hist_base) : kSentinelD;
-                kb.nslot = 0;
-            }
-        }
-        __syncthreads();
-        const unsigned long long T = kb.tslot;
-        if (T != kSentinelD) {
-            for (unsigned t = threadIdx.x; t < have; t += NT) {
-                const unsigned long long d = kb.bd[t];
-                if (d <= T) {
-                    const unsigned p = atomicAdd(&kb.nslot, 1u);
-                    if (p < kPassHeads) {
-                        kb.top_d[p] = d;
-                        kb.top_i[p] = kb.bi[t];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const unsigned ns = kb.nslot;
-        slotted = T != kSentinelD && ns <= kPassHeads;  // block-uniform
-        if (slotted && wid == 0) {
+        const unsigned long long T = kb.tslot;  // built before the barrier (kSentinelD: none)
+        // wave 0: the record from the ns <= kPassHeads slots in kb.top_*, as ONE store
+        // instruction -- lanes 0-7 a distance word each, lanes 8-11 two index words each, lane 12
+        // the length word (ns | kLenSlots); sentinel-padded.  Nothing goes to the list region:
+        // the final's list readers take a kLenSlots block's entries from its record (list_entry).
+        auto publish_slots = [&](unsigned ns) {
             PASS_TRACE(io, 8);
+            unsigned long long v = kSentinelD;
             if ((unsigned)lane < kPassHeads) {
-                const bool real = (unsigned)lane < ns;
-                const unsigned long long d = real ? kb.top_d[lane] : kSentinelD;
-                const unsigned i = real ? kb.top_i[lane] : kSentinelI;
-                store_wt(&io.head_d[kPassHeads * blockIdx.x + lane], d);
-                store_wt(&io.head_i[kPassHeads * blockIdx.x + lane], i);
-                if (real) {  // the list holds the same set (the final's fallback paths read lists)
-                    store_wt(&io.list_d[lbase + lane], d);
-                    store_wt(&io.list_i[lbase + lane], i);
-                }
+                if ((unsigned)lane < ns) v = kb.top_d[lane];
+            } else if ((unsigned)lane < kPassHeads + kPassHeads / 2) {
+                const unsigned j = 2u * ((unsigned)lane - kPassHeads);
+                const unsigned lo = j < ns ? kb.top_i[j] : kSentinelI;
+                const unsigned hi = j + 1 < ns ? kb.top_i[j + 1] : kSentinelI;
+                v = ((unsigned long long)hi << 32) | lo;
+            } else {
+                v = ns | kLenSlots;
             }
-            if (lane == 0) store_wt(&io.len[blockIdx.x], ns | kLenSlots);
+            if ((unsigned)lane <= kPassHeads + kPassHeads / 2) store_wt(rec_d(io, blockIdx.x) + lane, v);
             PASS_TRACE(io, 10);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             PASS_TRACE(io, 3);
             if (lane == 0) kb.last = pass_arrive_last(io.ctr + kTicketStride, io.groups) ? 1u : 0u;
+        };
+        if (have <= 4u * kWave) {
+            // common case: wave 0 alone, by ballot prefix, behind no further barrier
+            if (wid == 0 && T != kSentinelD) {
+                unsigned ns = 0;
+                unsigned long long sd[4];
+                unsigned si[4];
+#pragma unroll
+                for (unsigned u = 0; u < 4; u++) {  // all the LDS reads in flight at once
+                    const unsigned t = u * kWave + (unsigned)lane;
+                    sd[u] = t < have ? kb.bd[t] : kSentinelD;
+                    si[u] = t < have ? kb.bi[t] : kSentinelI;
+                }
+#pragma unroll
+                for (unsigned u = 0; u < 4; u++) {
+                    const bool keep = u * kWave + (unsigned)lane < have && sd[u] <= T;
+                    const unsigned long long m = __ballot(keep);
+                    const unsigned p = ns + lanes_below(m);
+                    if (keep && p < kPassHeads) {
+                        kb.top_d[p] = sd[u];
+                        kb.top_i[p] = si[u];
+                    }
+                    ns += (unsigned)__popcll(m);
+                }
+                wave_lds_sync();
+                slotted = ns <= kPassHeads;
+                if (slotted) publish_slots(ns);
+            }
+        } else {
+            if (T != kSentinelD) {
+                for (unsigned t = threadIdx.x; t < have; t += NT) {
+                    const unsigned long long d = kb.bd[t];
+                    if (d <= T) {
+                        const unsigned p = atomicAdd(&kb.nslot, 1u);
+                        if (p < kPassHeads) {
+                            kb.top_d[p] = d;
+                            kb.top_i[p] = kb.bi[t];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            const unsigned ns = kb.nslot;
+            slotted = T != kSentinelD && ns <= kPassHeads;
+            if (slotted && wid == 0) publish_slots(ns);
         }
     }
     auto bounds = [&](unsigned long long& Bv, unsigned long long& Hv) {  // wave 0
@@ -1515,17 +1672,17 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
         const bool small = (ms >> lane) & 1ull;
         const unsigned r = wave_rank_in(ms, d, i);
         if (small && r < kPassHeads) {
-            store_wt(&io.head_d[kPassHeads * blockIdx.x + r], d);
-            store_wt(&io.head_i[kPassHeads * blockIdx.x + r], i);
+            store_wt(rec_d(io, blockIdx.x) + r, d);
+            store_wt(rec_i(io, blockIdx.x) + r, i);
         }
         if ((unsigned)lane >= ns && (unsigned)lane < kPassHeads) {
-            store_wt(&io.head_d[kPassHeads * blockIdx.x + lane], kSentinelD);
-            store_wt(&io.head_i[kPassHeads * blockIdx.x + lane], kSentinelI);
+            store_wt(rec_d(io, blockIdx.x) + lane, kSentinelD);
+            store_wt(rec_i(io, blockIdx.x) + lane, kSentinelI);
         }
         // heads complete: every list entry <= H is among the ranked ones, and either kPassHeads
         // of them exist or the list holds nothing else
         const bool complete = ns <= (unsigned)kWave && (ns >= kPassHeads || ns == listed);
-        if (lane == 0) store_wt(&io.len[blockIdx.x], listed | (complete ? 0u : kLenWhole));
+        if (lane == 0) store_wt(rec_len(io, blockIdx.x), listed | (complete ? 0u : kLenWhole));
         PASS_TRACE(io, 10);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         PASS_TRACE(io, 3);
@@ -1644,14 +1801,20 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
                                        reinterpret_cast<unsigned*>(st.cx));
         return;
     }
+    // the final's histogram, veto and cursor words, armed before its first barrier
+    for (unsigned t = threadIdx.x; t < kHistBins; t += NT) kb.hist[t] = 0u;
     if (threadIdx.x == 0) {
+        kb.fin[1] = 0u;
+        kb.fin[2] = 0u;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
     PASS_TRACE(io, 5);
+    static_assert(kPassMaxBlocks * kPassHeads <= 2u * NT, "every record entry fits one rank_place pass (the direct final keeps those <= T)");
     // LDS for the final: the (idle) wave stages hold the gathered entries
     constexpr unsigned kGcap = (unsigned)(sizeof(stage) / 12) < 8u * NT ? (unsigned)(sizeof(stage) / 12) : 8u * NT;
+    static_assert(kGcap - (kGcap & 1u) >= kPassMaxBlocks * kPassHeads, "the gather holds every record entry");
     char* sb = reinterpret_cast<char*>(&stage[0]);
     unsigned long long* gd = reinterpret_cast<unsigned long long*>(sb);
     unsigned* gi = reinterpret_cast<unsigned*>(sb + (size_t)kGcap * 8);
@@ -1659,7 +1822,12 @@ __global__ __launch_bounds__(NW * 64) void knn_pass(const double* __restrict__ x
         const unsigned long long sp = load_sc1(io.ctr);  // the spill count the final re-arms
         pass_final<NT>(io, args, gd, gi, kGcap - (kGcap & 1u), kb.hist, kb.fin, kb.bd, kb.bi, kb.bi + kPassMaxBlocks);
         __syncthreads();
-        if (threadIdx.x == 0) store_wt(io.ctr, (unsigned)sp);
+        for (unsigned t = threadIdx.x; t < kHistBins; t += NT) kb.hist[t] = 0u;
+        if (threadIdx.x == 0) {
+            store_wt(io.ctr, (unsigned)sp);
+            kb.fin[1] = 0u;
+            kb.fin[2] = 0u;
+        }
         __syncthreads();
         PASS_TRACE(io, 5);
     }
@@ -2243,8 +2411,9 @@ void knn_pass_geometry(uint64_t n, unsigned* nblocks, uint64_t* chunk) {
     *nblocks = (unsigned)((n + c - 1) / c);
 }
 
+// per block its list region, then (in the distance array) every block's 128-byte record
 size_t knn_pass_list_entries(unsigned nblocks) {
-    return (size_t)nblocks * (PassBlock<kPassNW>::kCap + kPassHeads) + nblocks;
+    return (size_t)nblocks * (PassBlock<kPassNW>::kCap + kRecWords);
 }
 
 bool knn_pass_fuses_range(uint64_t n) {
@@ -2270,9 +2439,11 @@ hipError_t launch_knn_pass(const double* x, const double* y, uint64_t n, const K
     }
     const unsigned cap = (unsigned)PassBlock<kPassNW>::kCap;
     const size_t lists = (size_t)nblocks * cap;
-    // list entries, then the packed heads, then the list lengths (in the index array)
-    const PassIo io{list_d, list_i, cap, list_d + lists, list_i + lists, list_i + lists + (size_t)kPassHeads * nblocks,
-                    spill_d, nullptr, spill_i, ctr, out_d, out_i, out_count, 16u, trace};
+    // list entries, then the blocks' records (in the distance array: lists * 8 bytes is a multiple
+    // of 128, so the records are 128-byte aligned when the array is)
+    static_assert((PassBlock<kPassNW>::kCap * 8) % 128 == 0, "records start on a 128-byte line");
+    const PassIo io{list_d, list_i, cap, list_d + lists, spill_d, nullptr, spill_i, ctr, out_d, out_i, out_count, 16u,
+                    trace};
     PassRangeIo rio;
     memset(&rio, 0, sizeof rio);
     // ev0 / ev1 (timing on): stamped by the kernel's own dispatch begin / end
